@@ -11,14 +11,20 @@ One "step" = one pass of the hot path over the batch: polyCurveGeneration for ev
 (ddp_optimizer.cpp:5-438) in its phase-1 configuration (feasible IPDDP, launch-file weights), warm started
 from the phase-0 result and run for a FIXED 20 iterations with the early exits disabled so that every
 implementation does identical work.  Inputs are resident in HBM before the timed region,
-outputs stay in HBM.  After the timed region the same batch is solved once more with the reference's natural
-exits (secondary figure: rtn histogram, iterations to exit).
+outputs stay in HBM.
 
-`python bench.py --gpus N` with N > 1 and no torchrun environment re-executes itself under
-`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one rank per GPU over
-RCCL; launched by torchrun directly it reads RANK / LOCAL_RANK / WORLD_SIZE.  Ranks shard the problem stream
-(weak scaling, no data-path collective); the config-5 gather of the best trajectory (direct_ddp_gather_best:
-two ncclAllGather through the library's C entry point) runs once after the timed region.
+A plain run sets up, warms up, times --steps steps and prints one JSON line (roofline figures from the algorithmic
+words and the newest committed profiles of the workload).  `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<field>.npy.  `--full` adds everything else, after the timed region unless noted: the CPU baseline
+(before it), the config-5 gather, 100 sustained steps, host buffers, natural exits (rtn histogram, iterations to exit),
+the HBM copy, pipelined batches, one real corridor plan, the label model, corridor clusters and the live rocprofv3
+counter passes.
+
+`python bench.py --gpus N` with N > 1 and no torchrun environment starts itself under
+`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` in a child process, one rank
+per GPU over RCCL; launched by torchrun directly it reads RANK / LOCAL_RANK / WORLD_SIZE.  Ranks shard the problem
+stream (weak scaling, no data-path collective); with --full the config-5 gather of the best trajectory
+(direct_ddp_gather_best: two ncclAllGather through the library's C entry point) runs once after the timed region.
 """
 import argparse
 import glob
@@ -36,6 +42,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 F64_VECTOR_PEAK_TF = 78.6  # MI355X fp64 vector peak (same guide)
 FIXED_ITERS = 20
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together, .npy headers included
 CONFIGS = {  # BASELINE.json configs[1..4]
     2: dict(kind="free", batch=4096, nseg=100, dtype="f32", name="config 2"),
     3: dict(kind="corridor", batch=4096, nseg=100, dtype="f32", name="config 3"),
@@ -489,6 +496,24 @@ def pipelined_line(torch, dev, batch1, np_dt, params_fixed, batches=8):
     return out
 
 
+def dump_outputs(outs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """What the timed step hands its caller - every field of direct_ddp_batch_out_t - as out_dir/<field>.npy: floating
+    fields in their storage type, integer fields as float64 (exact).  When all rows do not fit in `limit` bytes, every
+    field keeps the same fixed, seeded sample of trajectories (rows, ascending)."""
+    import torch
+    fields = {k: (v if v.is_floating_point() else v.double()) for k, v in outs.t.items()}
+    B = next(iter(fields.values())).shape[0]
+    row_bytes = sum(v[0].numel() * v.element_size() for v in fields.values())
+    keep = (limit - 128 * len(fields)) // row_bytes   # 128 bytes: the header np.save writes for these shapes
+    if keep < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+        idx = torch.from_numpy(rows).to(next(iter(fields.values())).device)
+        fields = {k: v.index_select(0, idx) for k, v in fields.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in fields.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v.cpu().numpy())
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -531,15 +556,20 @@ def main():
     ap.add_argument("--nseg", type=int, default=0)
     ap.add_argument("--kind", default="", choices=["", "free", "corridor"])
     ap.add_argument("--dtype", default="", choices=["", "f32", "f64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the natural-exit run and the HBM copy microbench")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baseline, config-5 gather, secondary blocks and live counter passes")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the result arrays of the last timed step as DIR/<field>.npy (float32 / float64, at most "
+                         "64 MB in all: above that a fixed, seeded sample of trajectories)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary blocks")
     ap.add_argument("--with-secondary", action="store_true",
-                    help="N > 1 ranks: run the secondary blocks as well (by default a multi-GPU run times the headline step, "
-                         "runs the gather, and leaves: ~1 min of single-plan / label-model / cluster blocks on rank 0 would "
-                         "keep N - 1 leased GPUs waiting in a barrier)")
+                    help="--full with N > 1 ranks: run the secondary blocks as well (by default a multi-GPU run times the "
+                         "headline step, runs the gather, and leaves: ~1 min of single-plan / label-model / cluster blocks on "
+                         "rank 0 would keep N - 1 GPUs waiting in a barrier)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic in this run (two rocprofv3 --pmc passes of the same workload in a "
-                         "subprocess, ~30 s); the newest committed profile of the workload is quoted instead")
+                    help="--full without measuring roofline.traffic in this run (two rocprofv3 --pmc passes of the same "
+                         "workload in a subprocess, ~30 s); the newest committed profile of the workload is quoted instead")
     ap.add_argument("--dry", action="store_true",
                     help="no GPU: exercise launch, rendezvous (gloo), sharding and the gather on placeholder costs; "
                          "prints a line with value null (CPU test of the N > 1 plumbing, never a measurement)")
@@ -549,12 +579,17 @@ def main():
                          "split evenly over the GPUs")
     ap.add_argument("--total", type=int, default=131072, help="total corridors of a strong-scaling run (config 5's 131072)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if not args.full:
+        args.no_cpu_baseline = args.no_secondary = args.no_live_traffic = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the launcher of N ranks (one per GPU, RCCL)
+        # plain `python bench.py --gpus N`: launch N ranks (one per GPU, RCCL) in a child process
+        import subprocess
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
                "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.run(cmd).returncode)
 
     cfg = dict(CONFIGS[args.config])
     for k in ("batch", "nseg", "kind", "dtype"):
@@ -654,74 +689,79 @@ def main():
         dist.all_reduce(total, op=dist.ReduceOp.SUM)
     iters_all = float(total.item()) * args.steps
 
-    # config-5 reduction (functional check, untimed): cheapest feasible trajectory on every rank.
-    # (a) through torch.distributed, (b) through the library's C entry point on its own RCCL communicator.
-    cost_h, rtn_h = outs["cost"].cpu().numpy(), outs["rtn"].cpu().numpy()
-    li, lc = s.best_cost(outs["cost"].data_ptr(), outs["rtn"].data_ptr(), mem=abi.MEM_DEVICE, batch=B)
-    hi, hc = distributed.local_best(cost_h, rtn_h)
-    assert li == hi, (li, hi)
-    blk_src = max(li, 0)
-    block = torch.cat([outs["bez"][blk_src].reshape(-1), outs["T"][blk_src].reshape(-1)])
-    tg = time.perf_counter()
-    bc, bidx, owner, blk = distributed.gather_best(lc, first + li if li >= 0 else -1, block, force_collective=dist_on)
-    torch.cuda.synchronize()
-    gather = {"torch_ms": (time.perf_counter() - tg) * 1e3, "best_cost": bc, "best_index": bidx, "owner": owner,
-              "forced_dist_path": bool(dist_on and world == 1)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(outs, args.dump_outputs)
     devices = [local]
     if dist_on:  # every torch.distributed exchange the line needs happens BEFORE the library's own communicator is tried
         got = [None] * world
         dist.all_gather_object(got, (rank, local, torch.cuda.get_device_name(local)))
         devices = got
-        gather["dist_world_size"] = dist.get_world_size()
-    uid = [None]
-    try:
-        uid = [s.rccl_unique_id() if rank == 0 else None]
-    except Exception as e:  # noqa: BLE001
-        gather.update({"c_abi_error": repr(e)})
-    if dist_on:
-        dist.broadcast_object_list(uid, src=0)  # None: rank 0 could not talk to RCCL, nobody tries
 
-    def c_abi_gather(res):
-        """(b): the library's C entry point on its own RCCL communicator.  Runs in a thread with a deadline: a
-        communicator that cannot be built must cost the run this block, never the bench line."""
+    gather, rccl_hung = None, False
+    if args.full:
+        # config-5 reduction (functional check, untimed, --full): cheapest feasible trajectory on every rank.
+        # (a) through torch.distributed, (b) through the library's C entry point on its own RCCL communicator.
+        cost_h, rtn_h = outs["cost"].cpu().numpy(), outs["rtn"].cpu().numpy()
+        li, lc = s.best_cost(outs["cost"].data_ptr(), outs["rtn"].data_ptr(), mem=abi.MEM_DEVICE, batch=B)
+        hi, hc = distributed.local_best(cost_h, rtn_h)
+        assert li == hi, (li, hi)
+        blk_src = max(li, 0)
+        block = torch.cat([outs["bez"][blk_src].reshape(-1), outs["T"][blk_src].reshape(-1)])
+        tg = time.perf_counter()
+        bc, bidx, owner, blk = distributed.gather_best(lc, first + li if li >= 0 else -1, block, force_collective=dist_on)
+        torch.cuda.synchronize()
+        gather = {"torch_ms": (time.perf_counter() - tg) * 1e3, "best_cost": bc, "best_index": bidx, "owner": owner,
+                  "forced_dist_path": bool(dist_on and world == 1)}
+        if dist_on:
+            gather["dist_world_size"] = dist.get_world_size()
+        uid = [None]
         try:
-            comm = s.rccl_comm_create(uid[0], world, rank)
-            wb = torch.zeros(N, 18, dtype=outs["bez"].dtype, device=dev)
-            wT = torch.zeros(N, dtype=outs["T"].dtype, device=dev)
-            for rep in range(2):  # the second call is the timed one (the first builds RCCL's channels)
-                tg = time.perf_counter()
-                ci, cc, cown = s.gather_best(comm, world, rank, outs["cost"].data_ptr(), outs["rtn"].data_ptr(),
-                                             outs["bez"].data_ptr(), outs["T"].data_ptr(), first, mem=abi.MEM_DEVICE, batch=B,
-                                             out_bez=wb.data_ptr(), out_T=wT.data_ptr())
-                c_ms = (time.perf_counter() - tg) * 1e3
-            s.rccl_comm_destroy(comm)
-            same = (ci == bidx and cc == bc and cown == owner
-                    and bool(torch.equal(torch.cat([wb.reshape(-1), wT.reshape(-1)]), blk.to(dev))))
-            res.update({"c_abi_rccl_ms": c_ms, "c_abi_matches_torch": bool(same), "rccl_ranks": world})
-        except Exception as e:  # noqa: BLE001 - reported, not hidden
-            res.update({"c_abi_error": repr(e)})
+            uid = [s.rccl_unique_id() if rank == 0 else None]
+        except Exception as e:  # noqa: BLE001
+            gather.update({"c_abi_error": repr(e)})
+        if dist_on:
+            dist.broadcast_object_list(uid, src=0)  # None: rank 0 could not talk to RCCL, nobody tries
 
-    # RCCL writes a version banner to the C stdout when a communicator is created: keep this process's stdout
-    # for the ONE JSON line by pointing fd 1 at stderr while the library talks to RCCL
-    rccl_hung = False
-    if uid[0] is not None:
-        import ctypes
-        import threading
-        sys.stdout.flush()
-        saved_fd = os.dup(1)
-        os.dup2(2, 1)
-        res = {}
-        th = threading.Thread(target=c_abi_gather, args=(res,), daemon=True)
-        th.start()
-        th.join(timeout=120.0)
-        rccl_hung = th.is_alive()
-        ctypes.CDLL(None).fflush(None)
-        os.dup2(saved_fd, 1)
-        os.close(saved_fd)
-        gather.update(res if not rccl_hung else
-                      {"c_abi_error": "no answer from the library's RCCL communicator within 120 s; secondaries skipped"})
-    if rccl_hung:  # the handle's stream may be blocked behind a collective that never completes: nothing more runs on it
-        args.no_secondary = True
+        def c_abi_gather(res):
+            """(b): the library's C entry point on its own RCCL communicator.  Runs in a thread with a deadline: a
+            communicator that cannot be built must cost the run this block, never the bench line."""
+            try:
+                comm = s.rccl_comm_create(uid[0], world, rank)
+                wb = torch.zeros(N, 18, dtype=outs["bez"].dtype, device=dev)
+                wT = torch.zeros(N, dtype=outs["T"].dtype, device=dev)
+                for rep in range(2):  # the second call is the timed one (the first builds RCCL's channels)
+                    tg = time.perf_counter()
+                    ci, cc, cown = s.gather_best(comm, world, rank, outs["cost"].data_ptr(), outs["rtn"].data_ptr(),
+                                                 outs["bez"].data_ptr(), outs["T"].data_ptr(), first, mem=abi.MEM_DEVICE, batch=B,
+                                                 out_bez=wb.data_ptr(), out_T=wT.data_ptr())
+                    c_ms = (time.perf_counter() - tg) * 1e3
+                s.rccl_comm_destroy(comm)
+                same = (ci == bidx and cc == bc and cown == owner
+                        and bool(torch.equal(torch.cat([wb.reshape(-1), wT.reshape(-1)]), blk.to(dev))))
+                res.update({"c_abi_rccl_ms": c_ms, "c_abi_matches_torch": bool(same), "rccl_ranks": world})
+            except Exception as e:  # noqa: BLE001 - reported, not hidden
+                res.update({"c_abi_error": repr(e)})
+
+        # RCCL writes a version banner to the C stdout when a communicator is created: keep this process's stdout
+        # for the ONE JSON line by pointing fd 1 at stderr while the library talks to RCCL
+        if uid[0] is not None:
+            import ctypes
+            import threading
+            sys.stdout.flush()
+            saved_fd = os.dup(1)
+            os.dup2(2, 1)
+            res = {}
+            th = threading.Thread(target=c_abi_gather, args=(res,), daemon=True)
+            th.start()
+            th.join(timeout=120.0)
+            rccl_hung = th.is_alive()
+            ctypes.CDLL(None).fflush(None)
+            os.dup2(saved_fd, 1)
+            os.close(saved_fd)
+            gather.update(res if not rccl_hung else
+                          {"c_abi_error": "no answer from the library's RCCL communicator within 120 s; secondaries skipped"})
+        if rccl_hung:  # the handle's stream may be blocked behind a collective that never completes: nothing more runs on it
+            args.no_secondary = True
 
     # secondary: the same step sustained for 100 more launches (~4 s of uninterrupted GPU work: clocks settle, and an
     # outside sampler such as the driver's SMI poll gets to see the device busy; the headline value is NOT taken here)
@@ -866,8 +906,10 @@ def main():
                          traffic["traffic_bytes_per_launch"] / max(1, launch["bwd_knot_visits"] + launch["fwd_knot_visits"])},
             "kernel_ms_per_rank": rank_kernel_ms,
             "kernel_ms_rank_spread": (float(max(rank_kernel_ms) - min(rank_kernel_ms)) / float(np.mean(rank_kernel_ms))) if rank_kernel_ms else None,
-            "iters_per_step_rank0": iters_step, "gather": gather,
+            "iters_per_step_rank0": iters_step,
         }
+        if gather is not None:
+            line["gather"] = gather
         if sq is not None and "f64_flops_per_ddp_iteration" in sq["derived"] and "f64_arith_frac_of_valu" in sq["derived"]:
             fl = sq["derived"]["f64_flops_per_ddp_iteration"]
             tf = fl * (iters_step / (avg_ms * 1e-3)) / 1e12

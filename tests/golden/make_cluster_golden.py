@@ -9,6 +9,8 @@ serialConvexTest (oracle/_ref/libcluster_engine_ref.so, compiled from
   cluster_polygon_*.npz polygonGeneration for a few seeds: the loops around serialConvexTest are the restatement
                         of oracle/cluster_ref.c (cluster_server_cpu.cpp needs ROS headers and cannot be built),
                         run with the reference function plugged in.
+  cluster_convex_random_12.npz  twelve seeded random scenes (map, inside box, 60 candidates, a 6-voxel cluster) and
+                        serialConvexTest of every candidate against the cluster.
 Run from the repo root in the build container: python tests/golden/make_cluster_golden.py"""
 import os
 import sys
@@ -51,6 +53,30 @@ def convex_case(grid, seed, rounds):
         active = cand[accept == 1]
 
 
+def random_scenes(n=12):
+    """Seeded random scenes that exercise both outcomes of serialConvexTest, with the reference's answers."""
+    R = ca.ref_lib()
+    rng = np.random.default_rng(3)
+    out = dict(n=n)
+    for trial in range(n):
+        dims = (int(rng.integers(10, 40)), int(rng.integers(10, 40)), int(rng.integers(5, 16)))
+        grid = (rng.random(dims) < rng.uniform(0.002, 0.03)).astype(np.uint8)
+        inside = np.zeros(dims, np.uint8)
+        lo = [int(rng.integers(1, d // 2)) for d in dims]
+        hi = [int(rng.integers(d // 2, d - 1)) for d in dims]
+        inside[lo[0]:hi[0], lo[1]:hi[1], lo[2]:hi[2]] = 1
+        cand = np.stack([rng.integers(0, d, 60) for d in dims], 1).astype(np.int32)
+        clu = np.stack([rng.integers(0, d, 6) for d in dims], 1).astype(np.int32)
+        out.update({"grid_%d" % trial: grid, "inside_%d" % trial: inside, "cand_%d" % trial: cand, "cluster_%d" % trial: clu,
+                    "can_clu_%d" % trial: ca.serial_convex_test(R, "ref_serial_convex_test", cand, clu, inside, grid, dims)})
+    return out
+
+
+def write_random_scenes():
+    assert ca.ref_lib() is not None, "build oracle/_ref first (make -C oracle _ref)"
+    np.savez_compressed(os.path.join(OUT, "cluster_convex_random_12.npz"), **random_scenes())
+
+
 def main():
     assert ca.ref_lib() is not None, "build oracle/_ref first (make -C oracle _ref)"
     grid, seeds = problems.make_voxel_map((48, 48, 16), seed=11, n_pillars=22, n_boxes=10, n_rings=2)
@@ -72,6 +98,7 @@ def main():
     np.savez_compressed(os.path.join(OUT, "cluster_polygon_48.npz"), grid=grid, seeds=sel, vertex_idx=np.array(vs),
                         cluster_num=num, cluster_xyz=np.concatenate(cls), iters=np.array(its, np.int32))
     print("polygon: clusters", num.tolist(), "iters", its)
+    write_random_scenes()
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """Golden vectors for the hull -> planes step from the REFERENCE'S OWN convex hull (global_planner/third_party/quickhull,
 built from its sources into oracle/_ref/libquickhull_ref.so): for the 12 clusters of cluster_polygon_48.npz and four
 flat ones, the vertex buffer and the triangles getConvexHull(points, true, false) returns for the point set
-getConvexPoly builds (poly_utils.cpp:301-389).  Run in the build container (needs /root/reference):
+getConvexPoly builds (poly_utils.cpp:301-389); hull_quickhull_live_10.npz: the same for ten clusters the restated
+polygonGeneration grows on a seeded random map (tests/test_hull.py).  Needs oracle/_ref (the reference's sources, oracle/Makefile):
     python tests/golden/make_hull_golden.py
 """
 import os
@@ -10,7 +11,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
-from oracle import hullapi  # noqa: E402
+from oracle import clusterapi, hullapi  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -39,6 +40,36 @@ def main():
         out["qh_triangles_%d" % i] = tri.astype(np.int32)
     np.savez_compressed(os.path.join(HERE, "hull_quickhull_16.npz"), **out)
     print("wrote", len(clusters), "clusters")
+    write_live_clusters()
+
+
+def live_clusters(n=10):
+    """The clusters of tests/test_hull.py's seeded random map, with the reference's quickhull of their point sets."""
+    rng = np.random.default_rng(3)
+    grid = (rng.random((90, 90, 28)) < 0.006).astype(np.uint8)
+    out = dict(n=n)
+    done = 0
+    while done < n:
+        seed = [int(rng.integers(15, 75)), int(rng.integers(15, 75)), int(rng.integers(5, 23))]
+        if grid[tuple(seed)]:
+            continue
+        cl = clusterapi.polygon_generation(grid, seed)[1]
+        deg = hullapi.hull_planes(cl, 0.2, np.array([-12.0, -12.0, 0.0]))["degenerate"]
+        vb, tri = hullapi.reference_quickhull(hullapi.lattice_points(cl, deg).astype(np.float64))
+        vbq = np.rint(vb).astype(np.int32)
+        assert np.abs(vb - vbq).max() == 0
+        out["cluster_%d" % done] = cl.astype(np.int32)
+        out["deg_%d" % done] = int(deg)
+        out["qh_vertices_%d" % done] = vbq
+        out["qh_triangles_%d" % done] = tri.astype(np.int32)
+        done += 1
+    return out
+
+
+def write_live_clusters():
+    hullapi.build()
+    assert hullapi.ref_lib() is not None, "build oracle/_ref first (make -C oracle _ref)"
+    np.savez_compressed(os.path.join(HERE, "hull_quickhull_live_10.npz"), **live_clusters())
 
 
 if __name__ == "__main__":

@@ -206,14 +206,47 @@ def test_bench_distributed_branches_run_at_world_size_one(built):
     _torch()
     env = dict(os.environ, DIRECT_BENCH_FORCE_DIST="1", PYTHONPATH=ROOT)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "512", "--steps", "2", "--warmup", "1",
-                        "--no-secondary", "--no-cpu-baseline", "--no-live-traffic"], cwd=ROOT, env=env, capture_output=True,
-                       text=True, timeout=600)
+                        "--full", "--no-secondary", "--no-cpu-baseline", "--no-live-traffic"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     g = line["gather"]
     assert g["forced_dist_path"] is True and g["dist_world_size"] == 1
     assert g.get("rccl_ranks") == 1 and g.get("c_abi_matches_torch") is True, g
     assert line["n_gpus"] == 1 and line["value"] > 0 and len(line["kernel_ms_per_rank"]) == 1
+
+
+def test_bench_plain_run_dumps_what_the_timed_step_computed(built, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps, leaves the --full blocks out of its line, and --dump-outputs
+    writes the result arrays of the timed step: bit for bit what the same fixed-iteration phase-1 solve returns through
+    the host interface."""
+    import json
+    import subprocess
+    import sys
+    _torch()
+    B, N = 256, 100
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", str(B), "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["metric"] == "ddp_iterations_per_sec" and line["unit"] == "iter/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f64" and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert abs(line["value"] * line["ms_per_step"] - line["iters_per_step_rank0"] * 1e3) < 1e-6 * line["value"] * line["ms_per_step"]
+    assert not {"gather", "cpu_baseline", "natural_exit", "label_model", "pipelined"} & set(line)
+    got = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    batch = problems.make_batch("free", B, N, seed=1000, dtype=np.float32)
+    s = solver.DdpSolver(B, N, batch.p_max, np.float32)
+    g0 = s.solve(abi.phase0_params(), batch)
+    want = s.solve(abi.phase1_params(iter_max=20, fixed_iters=1), batch.phase1_inputs(g0))
+    s.close()
+    assert set(got) == {"rtn", "iter_used", "fwd_passes", "infeas_out", "line_failed_out", "cost", "costq", "jerk_cost",
+                        "terminal_norm2", "opterr", "mu", "bez", "poly", "T"}
+    for k, v in got.items():
+        assert np.array_equal(v, np.asarray(getattr(want, k)).astype(v.dtype)), k
 
 
 def test_config5_shard_fp32_and_c_abi_gather(built):

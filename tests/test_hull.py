@@ -7,7 +7,6 @@ not reproducible and are defined in include/direct_cluster.h."""
 import os
 
 import numpy as np
-import pytest
 
 from oracle import clusterapi, hullapi
 from tests.emu import hullemu
@@ -56,9 +55,11 @@ def test_oracle_against_the_reference_quickhull_golden():
         properties(cl, r)
 
 
-@pytest.mark.skipif(hullapi.ref_lib() is None and not os.path.exists("/root/reference"), reason="oracle/_ref not built")
 def test_oracle_against_the_reference_quickhull_live():
+    """Ten clusters grown on a seeded random map: the reference's quickhull of their point sets is committed
+    (tests/golden/make_hull_golden.py) and, where oracle/_ref is built, run again."""
     hullapi.build()
+    g = np.load(os.path.join(GOLD, "hull_quickhull_live_10.npz"))
     rng = np.random.default_rng(3)
     grid = (rng.random((90, 90, 28)) < 0.006).astype(np.uint8)
     done = 0
@@ -67,9 +68,12 @@ def test_oracle_against_the_reference_quickhull_live():
         if grid[tuple(seed)]:
             continue
         cl = clusterapi.polygon_generation(grid, seed)[1]
+        assert np.array_equal(cl, g["cluster_%d" % done])
         r = hullapi.hull_planes(cl, RES, LOWER)
-        assert r["rc"] == 0
-        hullapi.check_against_quickhull(hullapi.lattice_points(cl, r["degenerate"]), r["plane_int"], r["vert_q"])
+        assert r["rc"] == 0 and r["degenerate"] == g["deg_%d" % done]
+        hullapi.check_mesh(g["qh_vertices_%d" % done], g["qh_triangles_%d" % done], r["plane_int"], r["vert_q"])
+        if hullapi.ref_lib() is not None:
+            hullapi.check_against_quickhull(hullapi.lattice_points(cl, r["degenerate"]), r["plane_int"], r["vert_q"])
         done += 1
 
 

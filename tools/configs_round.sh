@@ -9,7 +9,7 @@ python - > $OUT/${R}_configs.json 2> $OUT/${R}_configs.err <<PY
 import json, subprocess, sys
 out = {}
 for c in (3, 4, 5, 6):
-    r = subprocess.run([sys.executable, "bench.py", "--config", str(c), "--steps", "5", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, "bench.py", "--config", str(c), "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline"], capture_output=True, text=True)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     out["config%d" % c] = json.loads(lines[-1]) if lines else {"error": r.stderr[-500:]}
 print(json.dumps(out, indent=1))

@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
-python bench.py > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err
+python bench.py --full > $OUT/${R}_bench.json 2> $OUT/${R}_bench.err
 cd /tmp && export TMPDIR=/tmp
 export PYTHONPATH=$ROOT
 rm -rf /tmp/prof_stats /tmp/pmc /tmp/cal_f /tmp/cal_w
