@@ -77,6 +77,70 @@ def with_extra_planes(batch, p_max, seed=0):
     return abi.HostBatch(batch.n_seg, batch.x0, batch.xd, batch.T0, n_planes, planes, seeds=batch.seeds, dtype=batch.dtype)
 
 
+# Plane counts where a knot's 6 P position rows end just below, on or just above a 64-row slot boundary, plus the edges of
+# the row-slot classes (6 P + 55 rows in 2 .. 8, 10, 12, 14 slots of 64: P <= 12, 22, 33, 44, 54, 65, 76, 97, 118, 128)
+EDGE_P = (6, 10, 11, 12, 13, 21, 22, 23, 32, 33, 34, 42, 43, 44, 45, 53, 54, 55, 64, 65, 66, 74, 75, 76, 77, 85, 86,
+          96, 97, 98, 106, 107, 117, 118, 119, 128)
+
+
+def row_class(p):
+    """row-slot class of the kernels that hold polytopes of up to p planes (direct_ddp.hip, rpl_class)"""
+    s = (6 * p + 55 + 63) // 64
+    return s if s <= 8 else (10 if s <= 10 else (12 if s <= 12 else 14))
+
+
+def ragged(batch, n_seg):
+    """the first n_seg[b] segments of every problem: the goal moves to the seed that ends them, durations re-allocated"""
+    from direct_amd import problems
+    n_seg = np.asarray(n_seg, np.int32)
+    xd = batch.xd.copy()
+    for b in range(batch.batch):
+        if n_seg[b] < batch.n_seg_max:
+            xd[b] = 0.0
+            xd[b, :3] = batch.seeds[b, n_seg[b]]
+    T0 = problems.time_allocation(n_seg, batch.x0[:, :3], xd[:, :3], batch.seeds)
+    return abi.HostBatch(n_seg, batch.x0, xd, T0, batch.n_planes, batch.planes, seeds=batch.seeds, dtype=batch.dtype)
+
+
+def with_edge_planes(batch, p_max, seed=0):
+    """Polytopes whose plane counts sit at the slot boundaries of the row-slot classes (EDGE_P).  p_max: one value, or one
+    per problem (the planes array is then as wide as the largest).  Knot 0 of problem b gets exactly p_max[b] planes, so
+    that the problem's class is the intended one; every other knot draws its count from EDGE_P up to p_max[b], with runs
+    of equal counts (row descriptors reused across knots, Wave::prefetch pk_valid) and changes between neighbours.  Counts
+    above the polytope's own are padded as in with_extra_planes (valid, mostly inactive half-spaces); counts below it drop
+    its last cutting planes (the first six, its bounding box, always stay)."""
+    rng = np.random.default_rng(seed)
+    B, nm, p0 = batch.planes.shape[:3]
+    pm = np.broadcast_to(np.asarray(p_max, np.int64), (B,))
+    width = max(int(pm.max()), p0)
+    planes = np.zeros((B, nm, width, 4))
+    planes[:, :, :p0] = batch.planes
+    n_planes = batch.n_planes.copy()
+    for b in range(B):
+        allowed = [p for p in EDGE_P if p <= pm[b]]
+        prev = int(pm[b])
+        for k in range(int(batch.n_seg[b])):
+            if k == 0:
+                target = int(pm[b])
+            elif rng.uniform() < 0.4:
+                target = prev
+            else:
+                target = int(allowed[rng.integers(len(allowed))])
+            prev = target
+            a = batch.x0[b, :3] if k == 0 else batch.seeds[b, k]
+            c = batch.xd[b, :3] if k == batch.n_seg[b] - 1 else batch.seeds[b, k + 1]
+            j = min(int(n_planes[b, k]), target)
+            planes[b, k, j:] = 0.0
+            while j < target:
+                n = rng.normal(size=3)
+                n /= np.linalg.norm(n)
+                off = max(float(n @ a), float(n @ c)) + float(rng.uniform(0.8, 3.0))   # both seeds strictly inside
+                planes[b, k, j] = np.r_[n, -off]
+                j += 1
+            n_planes[b, k] = target
+    return abi.HostBatch(batch.n_seg, batch.x0, batch.xd, batch.T0, n_planes, planes, seeds=batch.seeds, dtype=batch.dtype)
+
+
 # ---- fixtures of tests/golden/make_exit_golden.py: one per exit / failure branch of the outer loop (DDP:295-412) -------
 EXIT_CASES = ("exit_iter_max", "exit_neg_time", "exit_stuck_first", "exit_llt_retry", "exit_line_ok", "exit_line_no_update")
 _PARAM_FIELDS = ("max_vel", "max_acc", "w_snap", "w_terminal", "w_time", "iter_max", "time_power", "zero_init", "line_init",

@@ -7,7 +7,7 @@ import pytest
 
 from direct_amd import abi, problems
 from oracle import refapi
-from tests import helpers, stuck_lib
+from tests import helpers, row_class_lib, stuck_lib
 from tests.emu import emuapi
 
 
@@ -310,3 +310,20 @@ def test_phase1_inputs_reproduce_the_callers_hand_off_where_phase_0_fails():
     q0 = emuapi.solve_batch(abi.phase0_params(), batch)
     ok = q0.rtn == 2
     assert ok.any() and np.array_equal(batch.phase1_inputs(q0).init_poly[ok], q0.poly[ok])
+
+
+@pytest.mark.parametrize("p_max", row_class_lib.CLASS_EDGES)
+def test_stepped_iterates_at_every_row_slot_class_edge(p_max):
+    """The lowest and the highest p_max of every row-slot class (2 .. 8, 10, 12, 14 slots of 64 rows per lane), knots at the
+    slot boundaries (helpers.with_edge_planes: empty slots skipped by Wave::slot_on, row descriptors reused across runs of
+    equal plane counts), ragged n_seg.  Four single outer iterations of both phases next to the oracle: after each, every
+    discrete decision identical and X / U / S / Y (Y in infeasible mode) and the continuous scalars within 1e-10 per problem
+    (opterr: row_class_lib.check_scalars)."""
+    batch = row_class_lib.edge_batch(p_max, B=4)
+    for name, params, b in row_class_lib.phases(batch):
+        e, o = emuapi.EmuSolver(params, b), row_class_lib.Oracle(params, b)
+        worst, wsc = row_class_lib.stepped(e, o, params, b, K=4)
+        e.close()
+        o.close()
+        assert max(worst.values()) < 1e-10, (name, worst)
+        row_class_lib.check_scalars(wsc, 1e-10)
