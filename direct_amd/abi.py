@@ -85,6 +85,24 @@ class SampleOut(C.Structure):
     ]
 
 
+class EvalIn(C.Structure):  # direct_eval_in_t
+    _fields_ = [
+        ("batch", C.c_int32), ("n_seg_max", C.c_int32), ("m_max", C.c_int32), ("mem", C.c_int32),
+        ("n_seg", C.c_void_p), ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p),
+        ("n_query", C.c_void_p), ("t", C.c_void_p), ("t0", C.c_double), ("dt", C.c_double),
+    ]
+
+
+class EvalOut(C.Structure):  # direct_eval_out_t
+    _fields_ = [
+        ("status", C.c_void_p), ("t_total", C.c_void_p), ("seg", C.c_void_p), ("pos", C.c_void_p), ("vel", C.c_void_p),
+        ("acc", C.c_void_p), ("jerk", C.c_void_p), ("snap", C.c_void_p), ("state", C.c_void_p),
+    ]
+
+
+EVAL_OUTPUTS = ("t_total", "seg", "pos", "vel", "acc", "jerk", "snap", "state")   # the optional fields of EvalOut
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

@@ -6,6 +6,7 @@
 // without a gfx950 device direct_ddp_create() fails with DIRECT_ERR_NO_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,7 @@
 #include "../../include/direct_ddp.h"
 #include "ddp_wave.h"
 #include "traj_sample.h"
+#include "traj_eval.h"
 #include "corridor_io.h"
 #include "rccl_gather.h"
 
@@ -502,6 +504,10 @@ struct direct_ddp_handle_s {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
   bool sample_timed = false;
+  hipEvent_t eval_ev0 = nullptr, eval_ev1 = nullptr;  // direct_traj_eval_last_ms
+  bool eval_timed = false;
+  double* eval_S = nullptr;  // segment start times of the last direct_traj_eval_batch [batch][n_seg_max + 1] (grown on demand)
+  size_t eval_S_bytes = 0;
   int n_launches = 0;
   bool timed = false;
   // device buffers
@@ -986,6 +992,97 @@ static direct_status_t sample_t(direct_ddp_handle_t h, const direct_sample_in_t*
   return DIRECT_OK;
 }
 
+// direct_traj_eval_batch for one storage type: host arrays are staged through temporary device buffers as in sample_t
+template <typename Real>
+static direct_status_t eval_t(direct_ddp_handle_t h, const direct_eval_in_t* in, direct_eval_out_t* out) {
+  const size_t B = in->batch, nm = in->n_seg_max, M = in->m_max, r = sizeof(Real);
+  const bool host = in->mem == DIRECT_MEM_HOST;
+  const size_t s_bytes = B * (nm + 1) * sizeof(double);
+  if (h->eval_S_bytes < s_bytes) {  // hipFree waits for the kernels that still read the old workspace
+    if (h->eval_S) (void)hipFree(h->eval_S);
+    h->eval_S = nullptr;
+    h->eval_S_bytes = 0;
+    if (hipMalloc((void**)&h->eval_S, s_bytes) != hipSuccess) {
+      h->eval_S = nullptr;
+      return fail(DIRECT_ERR_DEVICE, "workspace of direct_traj_eval_batch");
+    }
+    h->eval_S_bytes = s_bytes;
+  }
+  std::vector<void*> tmp;
+  auto dev = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    tmp.push_back(q);
+    return q;
+  };
+  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
+  auto in_arr = [&](const void* src, size_t bytes) -> const void* {
+    if (!host || !src) return src;
+    void* q = dev(bytes);
+    if (q && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
+    return q;
+  };
+  // staged outputs are zero-filled: entries past n_query then read 0 on the host (device-resident outputs are left untouched)
+  auto out_arr = [&](void* dst, size_t bytes) -> void* {
+    if (!host || !dst) return dst;
+    void* q = dev(bytes);
+    if (q && hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) return nullptr;
+    return q;
+  };
+  EvalArgs<Real> A;
+  A.batch = in->batch; A.nmax = in->n_seg_max; A.m_max = in->m_max; A.poly = in->poly != nullptr; A.b_off = 0;
+  A.t0 = in->t0; A.dt = in->dt; A.S = h->eval_S;
+  A.n_seg = (const int32_t*)in_arr(in->n_seg, B * 4);
+  A.T = (const Real*)in_arr(in->T, B * nm * r);
+  A.coef = (const Real*)in_arr(A.poly ? in->poly : in->bez, B * nm * 18 * r);
+  A.n_query = (const int32_t*)in_arr(in->n_query, B * 4);
+  A.t = (const Real*)in_arr(in->t, B * M * r);
+  A.status = (int32_t*)out_arr(out->status, B * 4);
+  A.t_total = (Real*)out_arr(out->t_total, B * r);
+  A.seg = (int32_t*)out_arr(out->seg, B * M * 4);
+  void* const outs[5] = {out->pos, out->vel, out->acc, out->jerk, out->snap};
+  bool ok = A.n_seg && A.T && A.coef && A.status && (A.n_query || !in->n_query) && (A.t || !in->t) &&
+            (A.t_total || !out->t_total) && (A.seg || !out->seg);
+  for (int k = 0; k < 5; k++) {
+    A.out[k] = (Real*)out_arr(outs[k], B * M * 3 * r);
+    ok = ok && (A.out[k] || !outs[k]);
+  }
+  A.state = (Real*)out_arr(out->state, B * M * 9 * r);
+  ok = ok && (A.state || !out->state);
+  if (!ok) {
+    cleanup();
+    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_eval_batch");
+  }
+  const int chunks = (int)((M + kEvalChunk - 1) / kEvalChunk);
+  // the workspace S belongs to the handle: a call waits for the previous call's k_eval, on whichever stream that ran
+  if (h->eval_timed) (void)hipStreamWaitEvent(h->stream, h->eval_ev1, 0);
+  (void)hipEventRecord(h->eval_ev0, h->stream);
+  hipLaunchKernelGGL(k_eval_starts<Real>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, A);
+  for (int b0 = 0; b0 < in->batch; b0 += 65535) {  // gridDim.y is 16-bit
+    A.b_off = b0;
+    hipLaunchKernelGGL(k_eval<Real>, dim3(chunks, std::min(65535, in->batch - b0)), dim3(64), eval_lds_bytes(in->n_seg_max),
+                       h->stream, A);
+  }
+  (void)hipEventRecord(h->eval_ev1, h->stream);
+  h->eval_timed = true;
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && host) {
+    auto dn = [&](void* dst, const void* src, size_t bytes) {
+      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
+    };
+    if (e == hipSuccess) e = dn(out->status, A.status, B * 4);
+    if (e == hipSuccess) e = dn(out->t_total, A.t_total, B * r);
+    if (e == hipSuccess) e = dn(out->seg, A.seg, B * M * 4);
+    for (int k = 0; k < 5; k++)
+      if (e == hipSuccess) e = dn(outs[k], A.out[k], B * M * 3 * r);
+    if (e == hipSuccess) e = dn(out->state, A.state, B * M * 9 * r);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  }
+  if (host) { (void)hipStreamSynchronize(h->stream); cleanup(); }
+  if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("direct_traj_eval_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
 extern "C" {
 
 int32_t direct_ddp_abi_version(void) { return DIRECT_DDP_ABI_VERSION; }
@@ -1125,7 +1222,8 @@ direct_status_t direct_ddp_create(const direct_ddp_config_t* cfg, direct_ddp_han
   h->fieldbuf_bytes = B * nm * (size_t)std::max(ncm, 100) * r + B * 16 * r + B * 9 * r;
   A(&h->fieldbuf, h->fieldbuf_bytes);
   if (st == DIRECT_OK && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-                          hipEventCreate(&h->ev2) != hipSuccess || hipEventCreate(&h->ev3) != hipSuccess))
+                          hipEventCreate(&h->ev2) != hipSuccess || hipEventCreate(&h->ev3) != hipSuccess ||
+                          hipEventCreate(&h->eval_ev0) != hipSuccess || hipEventCreate(&h->eval_ev1) != hipSuccess))
     st = fail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
   if (st == DIRECT_OK && hipMemset(h->sched, 0, (B + 2) * sizeof(int)) != hipSuccess)
     st = fail(DIRECT_ERR_DEVICE, "hipMemset failed");
@@ -1160,6 +1258,9 @@ direct_status_t direct_ddp_destroy(direct_ddp_handle_t h) {
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->ev2) (void)hipEventDestroy(h->ev2);
   if (h->ev3) (void)hipEventDestroy(h->ev3);
+  if (h->eval_ev0) (void)hipEventDestroy(h->eval_ev0);
+  if (h->eval_ev1) (void)hipEventDestroy(h->eval_ev1);
+  if (h->eval_S) (void)hipFree(h->eval_S);
   delete h;
   return DIRECT_OK;
 }
@@ -1866,6 +1967,27 @@ direct_status_t direct_traj_sample_last_ms(direct_ddp_handle_t h, float* ms) {
   if (!h->sample_timed) return fail(DIRECT_ERR_INVALID, "no sampling launch to time");
   HIP_TRY(hipEventSynchronize(h->ev3));
   HIP_TRY(hipEventElapsedTime(ms, h->ev2, h->ev3));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_traj_eval_batch(direct_ddp_handle_t h, const direct_eval_in_t* in, direct_eval_out_t* out) {
+  if (!h || !in || !out) return fail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->n_seg_max <= 0 || in->m_max <= 0) return fail(DIRECT_ERR_INVALID, "bad sizes");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return fail(DIRECT_ERR_INVALID, "bad memory kind");
+  if (!in->n_seg || !in->T || !out->status) return fail(DIRECT_ERR_INVALID, "null array");
+  if ((in->bez == nullptr) == (in->poly == nullptr)) return fail(DIRECT_ERR_INVALID, "exactly one of bez and poly is needed");
+  if (!in->t && (!(in->dt > 0.0) || !std::isfinite(in->dt) || !std::isfinite(in->t0)))
+    return fail(DIRECT_ERR_INVALID, "grid times need a finite t0 and a finite dt > 0");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->dtype == DIRECT_F64) return eval_t<double>(h, in, out);
+  return eval_t<float>(h, in, out);
+}
+
+direct_status_t direct_traj_eval_last_ms(direct_ddp_handle_t h, float* ms) {
+  if (!h || !ms) return fail(DIRECT_ERR_INVALID, "null argument");
+  if (!h->eval_timed) return fail(DIRECT_ERR_INVALID, "no evaluation launch to time");
+  HIP_TRY(hipEventSynchronize(h->eval_ev1));
+  HIP_TRY(hipEventElapsedTime(ms, h->eval_ev0, h->eval_ev1));
   return DIRECT_OK;
 }
 

@@ -26,7 +26,7 @@ EXPORTS = (
     "direct_ddp_best_cost", "direct_ddp_sched_error", "direct_ddp_sched_debug", "direct_traj_sample_batch", "direct_traj_sample_last_ms",
     "direct_rccl_unique_id", "direct_rccl_comm_create", "direct_rccl_comm_destroy", "direct_ddp_gather_best",
     "direct_corridor_wire_size", "direct_corridor_pack", "direct_corridor_unpack", "direct_corridor_replay_batch",
-    "direct_ddp_last_launch_info", "direct_ddp_last_counters",
+    "direct_ddp_last_launch_info", "direct_ddp_last_counters", "direct_traj_eval_batch", "direct_traj_eval_last_ms",
 )
 
 
@@ -79,6 +79,8 @@ def lib():
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_traj_sample_batch.argtypes = [C.c_void_p] * 3
         L.direct_traj_sample_last_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.direct_traj_eval_batch.argtypes = [C.c_void_p] * 3
+        L.direct_traj_eval_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.direct_time_allocation.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_double, C.c_double, C.c_void_p]
         _LIB = L
@@ -251,6 +253,57 @@ class DdpSolver:
     def sample_last_ms(self):
         ms = C.c_float()
         _check(lib().direct_traj_sample_last_ms(self.h, C.addressof(ms)))
+        return ms.value
+
+    def evaluate(self, n_seg, T, *, bez=None, poly=None, times=None, t0=0.0, dt=None, m=None, n_query=None,
+                 outputs=("pos", "vel", "acc")):
+        """Trajectory evaluation at caller-given times, seconds from each trajectory's start (direct_traj_eval_batch).
+        Exactly one of bez / poly ([B][n_seg_max][18]); times [B][m], or None for the grid t0 + j * dt, j < m.  Host numpy
+        arrays in, dict of numpy arrays out: "status" and every name of `outputs` (abi.EVAL_OUTPUTS)."""
+        unknown = set(outputs) - set(abi.EVAL_OUTPUTS)
+        if unknown:
+            raise ValueError("unknown outputs: %s" % sorted(unknown))
+        n_seg = np.ascontiguousarray(n_seg, np.int32)
+        T = np.ascontiguousarray(T, self.np_dtype)
+        B, nm = T.shape
+        assert n_seg.shape == (B,), (n_seg.shape, B)
+        cin, cout = abi.EvalIn(), abi.EvalOut()
+        keep = []
+        for name, a in (("bez", bez), ("poly", poly)):
+            if a is not None:
+                a = np.ascontiguousarray(a, self.np_dtype).reshape(B, nm, 18)
+                keep.append(a)
+                setattr(cin, name, a.ctypes.data)
+        if times is not None:
+            times = np.ascontiguousarray(times, self.np_dtype).reshape(B, -1)
+            m = times.shape[1]
+            cin.t = times.ctypes.data
+        elif m is None:
+            raise ValueError("grid times need m")
+        if n_query is not None:
+            n_query = np.ascontiguousarray(n_query, np.int32)
+            assert n_query.shape == (B,), (n_query.shape, B)
+            cin.n_query = n_query.ctypes.data
+        cin.batch, cin.n_seg_max, cin.m_max, cin.mem = B, nm, int(m), abi.MEM_HOST
+        cin.n_seg, cin.T = n_seg.ctypes.data, T.ctypes.data
+        cin.t0, cin.dt = float(t0), float(0.0 if dt is None else dt)
+        shapes = dict(t_total=((B,), self.np_dtype), seg=((B, m), np.int32), state=((B, m, 9), self.np_dtype))
+        o = {"status": np.zeros(B, np.int32)}
+        for k in outputs:
+            shape, dtype = shapes.get(k, ((B, m, 3), self.np_dtype))
+            o[k] = np.zeros(shape, dtype)
+        for k, v in o.items():
+            setattr(cout, k, v.ctypes.data)
+        _check(lib().direct_traj_eval_batch(self.h, C.addressof(cin), C.addressof(cout)))
+        return o
+
+    def evaluate_device(self, cin, cout):
+        """direct_traj_eval_batch with caller-built abi.EvalIn / abi.EvalOut (device-resident arrays: asynchronous)."""
+        _check(lib().direct_traj_eval_batch(self.h, C.addressof(cin), C.addressof(cout)))
+
+    def eval_last_ms(self):
+        ms = C.c_float()
+        _check(lib().direct_traj_eval_last_ms(self.h, C.addressof(ms)))
         return ms.value
 
     # -- config-5 reduction through the C entry points (RCCL) ------------------------------------

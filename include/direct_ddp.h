@@ -293,6 +293,56 @@ direct_status_t direct_traj_sample_batch(direct_ddp_handle_t h, const direct_sam
 /* HIP-event time of the last direct_traj_sample_batch kernel on the handle's stream [ms] */
 direct_status_t direct_traj_sample_last_ms(direct_ddp_handle_t h, float* ms);
 
+/* ---- trajectory evaluation at caller-given times (no reference counterpart) ------------
+ * Position, velocity, acceleration, jerk and snap of solved trajectories on ONE clock: seconds from each trajectory's
+ * start, the same clock for every segment (the sampler above restarts time in every segment).  For the consumers of a plan:
+ * controller set-points (quadrotor_msgs/PositionCommand: p, v, a at a time stamp), the start state of a replan (`state` at
+ * t_now has the x0[b][9] layout of direct_ddp_batch_in_t), jerk / snap, several trajectories compared at common instants.
+ * All arithmetic is double, whatever the storage type.  With n = n_seg[b]:
+ *   1. segment start times S_0 = 0, S_(i+1) = S_i + T_i, summed in double left to right (numpy.cumsum);
+ *   2. clamping t_c = min(max(t, 0), S_n); a NaN time gives seg = -1 and NaN in every output of that query;
+ *   3. segment i = the largest index in [0, n-1] with S_i <= t_c: t == S_i is evaluated in segment i at its local time 0
+ *      (jerk and snap there are the later segment's);
+ *   4. from bez (getBezCoeff() layout, time-scaled control points): tau = min((t_c - S_i) / T_i, 1); the k-th time
+ *      derivative (k = 0..4) is T_i^(1-k) 5!/(5-k)! sum_j Delta^k c_j C(5-k, j) tau^j (1-tau)^(5-k-j)
+ *      (k <= 2: the sampler's formula);
+ *   5. from poly (getPolyCoeff() layout, row m of a segment's 6 x 3 block = coefficient of s^m): s = t_c - S_i, the
+ *      derivatives of sum_m a_m s^m in s.  In float storage prefer poly for jerk and snap: from control points they are
+ *      3rd and 4th differences of float numbers (see init_poly above);
+ *   6. a row is invalid when n lies outside [1, n_seg_max] or one of its first n durations is not a finite number > 0:
+ *      status = -1, t_total = 0, and seg = -1 and zeros in its first n_query entries; other rows are unaffected;
+ *   7. grid mode (t == NULL): t_j = t0 + (double)j * dt, the product rounded before the sum (t0 + numpy.arange(m) * dt);
+ *   8. entries past n_query[b] are left untouched in device memory and read zero in host memory.
+ * Real = the handle's dtype.  An output is computed only where its pointer is non-NULL.  DIRECT_ERR_INVALID, nothing
+ * launched: a NULL handle / struct / n_seg / T / status, a non-positive batch / n_seg_max / m_max, not exactly one of bez and
+ * poly, grid mode without a finite t0 and a finite dt > 0.  The contents of the arrays are judged on the device (item 6).
+ * Meant for batches: host-memory calls stage every array through temporary device buffers.  The segment start times live
+ * in one workspace per handle: each call waits for the previous call's kernels, also after direct_ddp_set_stream. */
+typedef struct {
+  int32_t batch, n_seg_max;
+  int32_t m_max;             /* queries per trajectory the time / output arrays hold (their stride) */
+  int32_t mem;               /* direct_mem_t: where every array of `in` and `out` lives */
+  const int32_t* n_seg;      /* [batch] */
+  const void* T;             /* [batch][n_seg_max] getPolyTime() */
+  const void* bez;           /* [batch][n_seg_max][18] or NULL } exactly one */
+  const void* poly;          /* [batch][n_seg_max][18] or NULL }            */
+  const int32_t* n_query;    /* [batch], clamped to [0, m_max]; NULL: m_max for every row */
+  const void* t;             /* [batch][m_max] seconds from the start; NULL: grid t0 + j * dt */
+  double t0, dt;
+} direct_eval_in_t;
+
+typedef struct {
+  int32_t* status;           /* [batch], required: 0 or -1 */
+  void* t_total;             /* [batch] S_n, or NULL */
+  int32_t* seg;              /* [batch][m_max] or NULL */
+  void *pos, *vel, *acc, *jerk, *snap;   /* [batch][m_max][3] each, or NULL */
+  void* state;               /* [batch][m_max][9] = pos, vel, acc: the x0 / xd layout, or NULL */
+} direct_eval_out_t;
+
+direct_status_t direct_traj_eval_batch(direct_ddp_handle_t h, const direct_eval_in_t* in, direct_eval_out_t* out);
+/* HIP-event time of the last direct_traj_eval_batch kernels on the handle's stream [ms] */
+direct_status_t direct_traj_eval_last_ms(direct_ddp_handle_t h, float* ms);
+
 /* ---- stepwise interface (per-pass parity tests and profiling) ------------------------ */
 /* begin: setup + initialroll + mu/filter/reg reset (ddp_optimizer.cpp:42-286). */
 direct_status_t direct_ddp_begin(direct_ddp_handle_t h, const direct_ddp_params_t* params,
