@@ -103,6 +103,30 @@ class EvalOut(C.Structure):  # direct_eval_out_t
 EVAL_OUTPUTS = ("t_total", "seg", "pos", "vel", "acc", "jerk", "snap", "state")   # the optional fields of EvalOut
 
 
+class AuditIn(C.Structure):  # direct_audit_in_t
+    _fields_ = [
+        ("batch", C.c_int32), ("n_seg_max", C.c_int32), ("p_max", C.c_int32), ("mem", C.c_int32),
+        ("n_seg", C.c_void_p), ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p),
+        ("n_planes", C.c_void_p), ("planes", C.c_void_p),
+        ("max_vel", C.c_double), ("max_acc", C.c_double), ("max_jerk", C.c_double), ("clearance", C.c_double),
+        ("limit_on_norm", C.c_int32), ("reserved", C.c_int32), ("cost", C.c_void_p), ("rtn", C.c_void_p),
+    ]
+
+
+class AuditOut(C.Structure):  # direct_audit_out_t
+    _fields_ = [
+        ("status", C.c_void_p), ("t_total", C.c_void_p), ("vpeak", C.c_void_p), ("apeak", C.c_void_p), ("jpeak", C.c_void_p),
+        ("vnorm", C.c_void_p), ("anorm", C.c_void_p), ("jnorm", C.c_void_p), ("cpeak", C.c_void_p), ("c_where", C.c_void_p),
+        ("at", C.c_void_p), ("seg_peak", C.c_void_p), ("gap", C.c_void_p), ("verdict", C.c_void_p), ("slowdown", C.c_void_p),
+        ("best", C.c_void_p),
+    ]
+
+
+AUDIT_OUTPUTS = ("t_total", "vpeak", "apeak", "jpeak", "vnorm", "anorm", "jnorm", "cpeak", "c_where", "at", "seg_peak", "gap",
+                 "verdict", "slowdown", "best")   # the optional fields of AuditOut
+AUDIT_VEL, AUDIT_ACC, AUDIT_JERK, AUDIT_CORRIDOR, AUDIT_INVALID = 1, 2, 4, 8, 256   # bits of `verdict` (0 = the plan passes)
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

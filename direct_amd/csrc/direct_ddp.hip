@@ -17,6 +17,7 @@
 #include "ddp_wave.h"
 #include "traj_sample.h"
 #include "traj_eval.h"
+#include "traj_audit.h"
 #include "corridor_io.h"
 #include "rccl_gather.h"
 
@@ -508,6 +509,10 @@ struct direct_ddp_handle_s {
   bool eval_timed = false;
   double* eval_S = nullptr;  // segment start times of the last direct_traj_eval_batch [batch][n_seg_max + 1] (grown on demand)
   size_t eval_S_bytes = 0;
+  hipEvent_t audit_ev0 = nullptr, audit_ev1 = nullptr;  // direct_traj_audit_last_ms
+  bool audit_timed = false;
+  char* audit_ws = nullptr;  // segment start times, per-segment records and verdicts of the last direct_traj_audit_batch (grown on demand)
+  size_t audit_ws_bytes = 0;
   int n_launches = 0;
   bool timed = false;
   // device buffers
@@ -1083,6 +1088,110 @@ static direct_status_t eval_t(direct_ddp_handle_t h, const direct_eval_in_t* in,
   return DIRECT_OK;
 }
 
+// direct_traj_audit_batch for one storage type: host arrays are staged through temporary device buffers as in eval_t
+template <typename Real>
+static direct_status_t audit_t(direct_ddp_handle_t h, const direct_audit_in_t* in, direct_audit_out_t* out) {
+  const size_t B = in->batch, nm = in->n_seg_max, r = sizeof(Real);
+  const bool host = in->mem == DIRECT_MEM_HOST, planes = in->planes != nullptr;
+  const size_t pm = planes ? in->p_max : 0;
+  const size_t ws_bytes = audit_ws_bytes(B, nm);
+  if (h->audit_ws_bytes < ws_bytes) {  // hipFree waits for the kernels that still use the old workspace
+    if (h->audit_ws) (void)hipFree(h->audit_ws);
+    h->audit_ws = nullptr;
+    h->audit_ws_bytes = 0;
+    if (hipMalloc((void**)&h->audit_ws, ws_bytes) != hipSuccess) {
+      h->audit_ws = nullptr;
+      return fail(DIRECT_ERR_DEVICE, "workspace of direct_traj_audit_batch");
+    }
+    h->audit_ws_bytes = ws_bytes;
+  }
+  std::vector<void*> tmp;
+  bool ok = true;
+  auto dev = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+    tmp.push_back(q);
+    return q;
+  };
+  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
+  auto in_arr = [&](const void* src, size_t bytes) -> const void* {
+    if (!host || !src) return src;
+    void* q = dev(bytes);
+    if (!q || hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ok = false;
+    return q;
+  };
+  // staged outputs are zero-filled: seg_peak entries past n_seg then read 0 on the host (device-resident outputs are left untouched)
+  auto out_arr = [&](void* dst, size_t bytes) -> void* {
+    if (!host || !dst) return dst;
+    void* q = dev(bytes);
+    if (!q || hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) ok = false;
+    return q;
+  };
+  AuditArgs<Real> A;
+  A.batch = in->batch; A.nmax = in->n_seg_max; A.pmax = (int)pm; A.poly = in->poly != nullptr; A.has_planes = planes;
+  A.norms = out->vnorm || out->anorm || out->jnorm || in->limit_on_norm;
+  A.lim = audit::Limits{in->max_vel, in->max_acc, in->max_jerk, in->clearance, in->limit_on_norm, planes};
+  A.S = (double*)h->audit_ws;
+  A.W = A.S + B * (nm + 1);
+  A.V = (int32_t*)(A.W + B * nm * audit::kWs);
+  A.n_seg = (const int32_t*)in_arr(in->n_seg, B * 4);
+  A.T = (const Real*)in_arr(in->T, B * nm * r);
+  A.coef = (const Real*)in_arr(A.poly ? in->poly : in->bez, B * nm * 18 * r);
+  A.n_planes = (const int32_t*)in_arr(in->n_planes, B * nm * 4);
+  A.planes = (const Real*)in_arr(in->planes, B * nm * pm * 4 * r);
+  A.cost = (const Real*)in_arr(in->cost, B * r);
+  A.rtn = (const int32_t*)in_arr(in->rtn, B * 4);
+  A.status = (int32_t*)out_arr(out->status, B * 4);
+  A.t_total = (Real*)out_arr(out->t_total, B * r);
+  void* const peaks[7] = {out->vpeak, out->apeak, out->jpeak, out->vnorm, out->anorm, out->jnorm, out->cpeak};
+  for (int k = 0; k < 7; k++) A.peak[k] = (Real*)out_arr(peaks[k], B * r);
+  A.c_where = (int32_t*)out_arr(out->c_where, B * 2 * 4);
+  A.at = (Real*)out_arr(out->at, B * 4 * r);
+  A.seg_peak = (Real*)out_arr(out->seg_peak, B * nm * 4 * r);
+  A.gap = (Real*)out_arr(out->gap, B * 3 * r);
+  A.verdict = (int32_t*)out_arr(out->verdict, B * 4);
+  A.slowdown = (Real*)out_arr(out->slowdown, B * r);
+  A.best = (long long*)out_arr(out->best, 8);
+  if (!ok) {
+    if (host) (void)hipStreamSynchronize(h->stream);
+    cleanup();
+    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_audit_batch");
+  }
+  // the workspace belongs to the handle: a call waits for the previous call's kernels, on whichever stream they ran
+  if (h->audit_timed) (void)hipStreamWaitEvent(h->stream, h->audit_ev1, 0);
+  (void)hipEventRecord(h->audit_ev0, h->stream);
+  hipLaunchKernelGGL(k_audit_starts<Real>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, A);
+  const unsigned waves = (unsigned)((B * nm + kAuditSeg - 1) / kAuditSeg);
+  if (A.poly)
+    hipLaunchKernelGGL((k_audit_items<true, Real>), dim3(waves), dim3(64), 0, h->stream, A);
+  else
+    hipLaunchKernelGGL((k_audit_items<false, Real>), dim3(waves), dim3(64), 0, h->stream, A);
+  hipLaunchKernelGGL(k_audit_rows<Real>, dim3((unsigned)B), dim3(64), 0, h->stream, A);
+  if (A.best) hipLaunchKernelGGL(k_audit_best<Real>, dim3(1), dim3(256), 0, h->stream, A);
+  (void)hipEventRecord(h->audit_ev1, h->stream);
+  h->audit_timed = true;
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess && host) {
+    auto dn = [&](void* dst, const void* src, size_t bytes) {
+      if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
+    };
+    dn(out->status, A.status, B * 4);
+    dn(out->t_total, A.t_total, B * r);
+    for (int k = 0; k < 7; k++) dn(peaks[k], A.peak[k], B * r);
+    dn(out->c_where, A.c_where, B * 2 * 4);
+    dn(out->at, A.at, B * 4 * r);
+    dn(out->seg_peak, A.seg_peak, B * nm * 4 * r);
+    dn(out->gap, A.gap, B * 3 * r);
+    dn(out->verdict, A.verdict, B * 4);
+    dn(out->slowdown, A.slowdown, B * r);
+    dn(out->best, A.best, 8);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+  }
+  if (host) { (void)hipStreamSynchronize(h->stream); cleanup(); }
+  if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("direct_traj_audit_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
 extern "C" {
 
 int32_t direct_ddp_abi_version(void) { return DIRECT_DDP_ABI_VERSION; }
@@ -1223,7 +1332,8 @@ direct_status_t direct_ddp_create(const direct_ddp_config_t* cfg, direct_ddp_han
   A(&h->fieldbuf, h->fieldbuf_bytes);
   if (st == DIRECT_OK && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
                           hipEventCreate(&h->ev2) != hipSuccess || hipEventCreate(&h->ev3) != hipSuccess ||
-                          hipEventCreate(&h->eval_ev0) != hipSuccess || hipEventCreate(&h->eval_ev1) != hipSuccess))
+                          hipEventCreate(&h->eval_ev0) != hipSuccess || hipEventCreate(&h->eval_ev1) != hipSuccess ||
+                          hipEventCreate(&h->audit_ev0) != hipSuccess || hipEventCreate(&h->audit_ev1) != hipSuccess))
     st = fail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
   if (st == DIRECT_OK && hipMemset(h->sched, 0, (B + 2) * sizeof(int)) != hipSuccess)
     st = fail(DIRECT_ERR_DEVICE, "hipMemset failed");
@@ -1261,6 +1371,9 @@ direct_status_t direct_ddp_destroy(direct_ddp_handle_t h) {
   if (h->eval_ev0) (void)hipEventDestroy(h->eval_ev0);
   if (h->eval_ev1) (void)hipEventDestroy(h->eval_ev1);
   if (h->eval_S) (void)hipFree(h->eval_S);
+  if (h->audit_ev0) (void)hipEventDestroy(h->audit_ev0);
+  if (h->audit_ev1) (void)hipEventDestroy(h->audit_ev1);
+  if (h->audit_ws) (void)hipFree(h->audit_ws);
   delete h;
   return DIRECT_OK;
 }
@@ -1988,6 +2101,32 @@ direct_status_t direct_traj_eval_last_ms(direct_ddp_handle_t h, float* ms) {
   if (!h->eval_timed) return fail(DIRECT_ERR_INVALID, "no evaluation launch to time");
   HIP_TRY(hipEventSynchronize(h->eval_ev1));
   HIP_TRY(hipEventElapsedTime(ms, h->eval_ev0, h->eval_ev1));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_traj_audit_batch(direct_ddp_handle_t h, const direct_audit_in_t* in, direct_audit_out_t* out) {
+  if (!h || !in || !out) return fail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->n_seg_max <= 0) return fail(DIRECT_ERR_INVALID, "bad sizes");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return fail(DIRECT_ERR_INVALID, "bad memory kind");
+  if (!in->n_seg || !in->T || !out->status) return fail(DIRECT_ERR_INVALID, "null array");
+  if ((in->bez == nullptr) == (in->poly == nullptr)) return fail(DIRECT_ERR_INVALID, "exactly one of bez and poly is needed");
+  if ((in->planes == nullptr) != (in->n_planes == nullptr) || (in->planes && in->p_max <= 0))
+    return fail(DIRECT_ERR_INVALID, "the corridor needs planes, n_planes and p_max: all three or none");
+  if (!in->planes && (out->cpeak || out->c_where)) return fail(DIRECT_ERR_INVALID, "cpeak and c_where need the corridor");
+  if (std::isnan(in->max_vel) || std::isnan(in->max_acc) || std::isnan(in->max_jerk)) return fail(DIRECT_ERR_INVALID, "a limit is NaN");
+  if (!(in->clearance >= 0.0)) return fail(DIRECT_ERR_INVALID, "clearance must be >= 0");
+  if (in->limit_on_norm != 0 && in->limit_on_norm != 1) return fail(DIRECT_ERR_INVALID, "limit_on_norm must be 0 or 1");
+  if (out->best && !in->cost) return fail(DIRECT_ERR_INVALID, "best needs cost");
+  HIP_TRY(hipSetDevice(h->device));
+  if (h->dtype == DIRECT_F64) return audit_t<double>(h, in, out);
+  return audit_t<float>(h, in, out);
+}
+
+direct_status_t direct_traj_audit_last_ms(direct_ddp_handle_t h, float* ms) {
+  if (!h || !ms) return fail(DIRECT_ERR_INVALID, "null argument");
+  if (!h->audit_timed) return fail(DIRECT_ERR_INVALID, "no audit launch to time");
+  HIP_TRY(hipEventSynchronize(h->audit_ev1));
+  HIP_TRY(hipEventElapsedTime(ms, h->audit_ev0, h->audit_ev1));
   return DIRECT_OK;
 }
 

@@ -350,4 +350,70 @@ std::vector<std::array<double, 3>> sampleBezierTrajectory(DdpDevice& dev, const 
   return pts;
 }
 
+// The continuous-time audit (direct_traj_audit_batch) of ONE plan: may it be flown?  polyCoeff = getPolyCoeff() (N x 18),
+// time = getPolyTime(), the corridor the plan was solved in, and the limits (a limit <= 0 is not judged; max_jerk is the
+// launch file's max_jer, which the optimiser itself ignores).  Batched callers use direct_traj_audit_batch directly.
+struct PlanAudit {
+  int verdict = DIRECT_AUDIT_INVALID;  // DIRECT_AUDIT_* bits; 0 = the plan passes
+  double vpeak = 0, apeak = 0, jpeak = 0, vnorm = 0, anorm = 0, jnorm = 0;
+  double cpeak = 0;                    // <= 0 iff the whole curve lies in its corridor
+  double at[4] = {0, 0, 0, 0};         // seconds from the start of vpeak, apeak, jpeak, cpeak
+  int c_segment = 0, c_plane = 0;      // where cpeak occurs
+  double gap[3] = {0, 0, 0};           // largest jump of position, velocity, acceleration across segment boundaries
+  double slowdown = 0;                 // T_i -> slowdown * T_i keeps the judged limits
+  double t_total = 0;
+  bool ok() const { return verdict == 0; }
+};
+template <class Corridor, class Mat, class Vec>
+PlanAudit auditTrajectory(DdpDevice& dev, const Mat& polyCoeff, const Vec& time, const Corridor& corridor, double max_vel,
+                          double max_acc, double max_jerk, double clearance = 0.0, bool limit_on_norm = false) {
+  const int N = (int)time.size();
+  const bool f64 = dev.dtype() == DIRECT_F64;
+  int pm = 1;
+  for (int k = 0; k < N && k < (int)corridor.polyhedrons.size(); k++) pm = std::max(pm, (int)corridor.polyhedrons[k].planes.size());
+  std::vector<double> poly((size_t)N * 18), T(N), planes((size_t)N * pm * 4, 0.0), real(21, 0.0);
+  std::vector<int32_t> n_planes(N, 0);
+  for (int k = 0; k < N; k++) {
+    T[k] = time(k);
+    for (int q = 0; q < 18; q++) poly[(size_t)k * 18 + q] = polyCoeff(k, q);
+    if (k >= (int)corridor.polyhedrons.size()) continue;  // n_planes = 0: the row is reported invalid
+    const auto& pl = corridor.polyhedrons[k].planes;
+    n_planes[k] = (int32_t)pl.size();
+    for (size_t j = 0; j < pl.size(); j++)
+      for (int c = 0; c < 4; c++) planes[((size_t)k * pm + j) * 4 + c] = elem(pl[j], c);
+  }
+  std::vector<float> fpoly, fT, fplanes, freal;
+  int32_t n_seg = N, status = 0, verdict = 0, c_where[2] = {0, 0};
+  direct_audit_in_t in{};
+  in.batch = 1; in.n_seg_max = N; in.p_max = pm; in.mem = DIRECT_MEM_HOST; in.n_seg = &n_seg; in.n_planes = n_planes.data();
+  in.max_vel = max_vel; in.max_acc = max_acc; in.max_jerk = max_jerk; in.clearance = clearance; in.limit_on_norm = limit_on_norm ? 1 : 0;
+  direct_audit_out_t out{};
+  out.status = &status; out.verdict = &verdict; out.c_where = c_where;
+  char* r = (char*)real.data();
+  size_t sz = sizeof(double);
+  if (f64) {
+    in.poly = poly.data(); in.T = T.data(); in.planes = planes.data();
+  } else {
+    fpoly.assign(poly.begin(), poly.end()); fT.assign(T.begin(), T.end()); fplanes.assign(planes.begin(), planes.end());
+    freal.assign(real.size(), 0.0f);
+    in.poly = fpoly.data(); in.T = fT.data(); in.planes = fplanes.data();
+    r = (char*)freal.data();
+    sz = sizeof(float);
+  }
+  // one array of reals: t_total, the seven peaks, slowdown, at[4], gap[3]
+  out.t_total = r; out.vpeak = r + sz; out.apeak = r + 2 * sz; out.jpeak = r + 3 * sz; out.vnorm = r + 4 * sz; out.anorm = r + 5 * sz;
+  out.jnorm = r + 6 * sz; out.cpeak = r + 7 * sz; out.slowdown = r + 8 * sz; out.at = r + 9 * sz; out.gap = r + 13 * sz;
+  if (direct_traj_audit_batch(dev.handle(), &in, &out) != DIRECT_OK) throw std::runtime_error(direct_ddp_last_error());
+  auto get = [&](int i) { return f64 ? real[i] : (double)freal[i]; };
+  PlanAudit a;
+  a.verdict = verdict;
+  a.t_total = get(0); a.vpeak = get(1); a.apeak = get(2); a.jpeak = get(3); a.vnorm = get(4); a.anorm = get(5); a.jnorm = get(6);
+  a.cpeak = get(7); a.slowdown = get(8);
+  for (int q = 0; q < 4; q++) a.at[q] = get(9 + q);
+  for (int q = 0; q < 3; q++) a.gap[q] = get(13 + q);
+  a.c_segment = c_where[0];
+  a.c_plane = c_where[1];
+  return a;
+}
+
 }  // namespace direct

@@ -27,6 +27,7 @@ EXPORTS = (
     "direct_rccl_unique_id", "direct_rccl_comm_create", "direct_rccl_comm_destroy", "direct_ddp_gather_best",
     "direct_corridor_wire_size", "direct_corridor_pack", "direct_corridor_unpack", "direct_corridor_replay_batch",
     "direct_ddp_last_launch_info", "direct_ddp_last_counters", "direct_traj_eval_batch", "direct_traj_eval_last_ms",
+    "direct_traj_audit_batch", "direct_traj_audit_last_ms",
 )
 
 
@@ -81,6 +82,8 @@ def lib():
         L.direct_traj_sample_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.direct_traj_eval_batch.argtypes = [C.c_void_p] * 3
         L.direct_traj_eval_last_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.direct_traj_audit_batch.argtypes = [C.c_void_p] * 3
+        L.direct_traj_audit_last_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.direct_time_allocation.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_double, C.c_double, C.c_void_p]
         _LIB = L
@@ -304,6 +307,66 @@ class DdpSolver:
     def eval_last_ms(self):
         ms = C.c_float()
         _check(lib().direct_traj_eval_last_ms(self.h, C.addressof(ms)))
+        return ms.value
+
+    def audit(self, n_seg, T, *, bez=None, poly=None, n_planes=None, planes=None, max_vel=0.0, max_acc=0.0, max_jerk=0.0,
+              clearance=0.0, limit_on_norm=False, cost=None, rtn=None, outputs=None):
+        """Continuous-time audit of solved plans (direct_traj_audit_batch): exact peaks of velocity, acceleration and jerk,
+        corridor clearance of the whole curve, verdict, slowdown and the cheapest plan that passes.  Exactly one of bez / poly
+        ([B][n_seg_max][18]); the corridor (n_planes, planes) is optional.  Host numpy arrays in, dict of numpy arrays out:
+        "status" and every name of `outputs` (abi.AUDIT_OUTPUTS; default: all that the inputs allow)."""
+        if outputs is None:
+            outputs = [k for k in abi.AUDIT_OUTPUTS
+                       if not (k in ("cpeak", "c_where") and planes is None) and not (k == "best" and cost is None)]
+        unknown = set(outputs) - set(abi.AUDIT_OUTPUTS)
+        if unknown:
+            raise ValueError("unknown outputs: %s" % sorted(unknown))
+        n_seg = np.ascontiguousarray(n_seg, np.int32)
+        T = np.ascontiguousarray(T, self.np_dtype)
+        B, nm = T.shape
+        assert n_seg.shape == (B,), (n_seg.shape, B)
+        cin, cout = abi.AuditIn(), abi.AuditOut()
+        keep = []
+        for name, a in (("bez", bez), ("poly", poly)):
+            if a is not None:
+                a = np.ascontiguousarray(a, self.np_dtype).reshape(B, nm, 18)
+                keep.append(a)
+                setattr(cin, name, a.ctypes.data)
+        if planes is not None:
+            planes = np.ascontiguousarray(planes, self.np_dtype)
+            assert planes.shape[:2] == (B, nm) and planes.shape[3] == 4, planes.shape
+            cin.p_max, cin.planes = planes.shape[2], planes.ctypes.data
+        if n_planes is not None:
+            n_planes = np.ascontiguousarray(n_planes, np.int32).reshape(B, nm)
+            cin.n_planes = n_planes.ctypes.data
+        if cost is not None:
+            cost = np.ascontiguousarray(cost, self.np_dtype).reshape(B)
+            cin.cost = cost.ctypes.data
+        if rtn is not None:
+            rtn = np.ascontiguousarray(rtn, np.int32).reshape(B)
+            cin.rtn = rtn.ctypes.data
+        cin.batch, cin.n_seg_max, cin.mem = B, nm, abi.MEM_HOST
+        cin.n_seg, cin.T = n_seg.ctypes.data, T.ctypes.data
+        cin.max_vel, cin.max_acc, cin.max_jerk, cin.clearance = float(max_vel), float(max_acc), float(max_jerk), float(clearance)
+        cin.limit_on_norm = int(bool(limit_on_norm))
+        shapes = dict(c_where=((B, 2), np.int32), at=((B, 4), self.np_dtype), seg_peak=((B, nm, 4), self.np_dtype),
+                      gap=((B, 3), self.np_dtype), verdict=((B,), np.int32), best=((1,), np.int64))
+        o = {"status": np.zeros(B, np.int32)}
+        for k in outputs:
+            shape, dtype = shapes.get(k, ((B,), self.np_dtype))
+            o[k] = np.zeros(shape, dtype)
+        for k, v in o.items():
+            setattr(cout, k, v.ctypes.data)
+        _check(lib().direct_traj_audit_batch(self.h, C.addressof(cin), C.addressof(cout)))
+        return o
+
+    def audit_device(self, cin, cout):
+        """direct_traj_audit_batch with caller-built abi.AuditIn / abi.AuditOut (device-resident arrays: asynchronous)."""
+        _check(lib().direct_traj_audit_batch(self.h, C.addressof(cin), C.addressof(cout)))
+
+    def audit_last_ms(self):
+        ms = C.c_float()
+        _check(lib().direct_traj_audit_last_ms(self.h, C.addressof(ms)))
         return ms.value
 
     # -- config-5 reduction through the C entry points (RCCL) ------------------------------------

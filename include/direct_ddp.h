@@ -343,6 +343,94 @@ direct_status_t direct_traj_eval_batch(direct_ddp_handle_t h, const direct_eval_
 /* HIP-event time of the last direct_traj_eval_batch kernels on the handle's stream [ms] */
 direct_status_t direct_traj_eval_last_ms(direct_ddp_handle_t h, float* ms);
 
+/* ---- continuous-time audit of solved plans (no reference counterpart) ------------------
+ * May this plan be flown?  rtn >= 0 does not say so: rtn = 0 also means "ran to iter_max", the solver's limits are rows on
+ * control points, and vmax / amax / cmax of the sampler above are maxima over SAMPLES.  This call gives the certificate: the
+ * true maxima over continuous time of velocity, acceleration and jerk, where they occur on the plan's clock, whether the
+ * whole curve stays in its corridor and with what margin, a verdict word per plan, and the cheapest plan that passes.
+ * batch, n_seg_max, mem, n_seg, T and exactly one of bez / poly: meaning, layouts and row validity as in direct_eval_in_t
+ * (items 1 and 6 there).  The corridor (p_max, n_planes, planes as in direct_ddp_batch_in_t) is optional: all three or none.
+ * All arithmetic is double, whatever the storage type.  For a valid row of n segments, segment i is the quintic p_i(s),
+ * s in [0, T_i] (poly: the stored coefficients; bez: p_i(T_i tau) = T_i sum_j c_j B_j(tau)); both ends of a segment count.
+ *   1. vpeak, apeak, jpeak [batch]: the maximum over segments, axes d and s of |p'_d|, |p''_d|, |p'''_d|;
+ *      vnorm, anorm, jnorm [batch]: the same with the Euclidean norm over the three axes.
+ *   2. cpeak [batch] (needs the corridor): the maximum over segments i, planes k < n_planes[b][i] of segment i's own polytope
+ *      and s of a x + b y + c z + d at p_i(s): cpeak <= 0 iff the whole curve lies in its corridor.
+ *      c_where [batch][2]: that segment and plane.
+ *   3. at [batch][4]: the time S_i + s on the plan's clock (S as in the evaluation) of vpeak, apeak, jpeak, cpeak (0 without a
+ *      corridor).  Ties: the earliest time, then (cpeak) the earlier segment, then the smallest plane index.  This is a total
+ *      order: no result depends on the launch shape or on which other rows share the call.
+ *   4. seg_peak [batch][n_seg_max][4]: the four quantities of items 1 (per axis) and 2 for each segment alone.  Entries past
+ *      n_seg are untouched in device memory and zero in host memory; the first min(n_seg, n_seg_max) of an invalid row are zero.
+ *   5. gap [batch][3]: the largest jump (max over axes) of position, velocity, acceleration across the interior segment
+ *      boundaries, |p_i^(k)(T_i) - p_(i+1)^(k)(0)|; 0 when n = 1.  Zero in exact arithmetic for a solved plan; float storage
+ *      and hand-edited plans differ.
+ *   6. verdict [batch]: DIRECT_AUDIT_VEL / _ACC / _JERK set when the judged peak - per axis with limit_on_norm = 0 (the
+ *      solver's own rows, |v_d| <= max_vel for each axis), Euclidean with 1 - is > its limit (a limit <= 0 is not judged);
+ *      DIRECT_AUDIT_CORRIDOR when a corridor is given and cpeak > -clearance; DIRECT_AUDIT_INVALID alone for an invalid row;
+ *      0 = the plan passes.  Decided in double, before any output is rounded to float.
+ *   7. slowdown [batch]: max(1, v / max_vel, sqrt(a / max_acc), cbrt(j / max_jerk)) over the judged limits and peaks: the
+ *      uniform dilation T_i -> lambda T_i after which the plan keeps them (the path, and so cpeak, do not change).
+ *   8. status [batch] (required), t_total [batch] as in the evaluation.  A row is also invalid when a corridor is given and an
+ *      n_planes entry of its first n segments lies outside [1, p_max], or when a coefficient, or an entry of a plane
+ *      k < n_planes, of those segments is not finite.  Invalid rows: status = -1, verdict = DIRECT_AUDIT_INVALID, zeros
+ *      elsewhere; other rows are unaffected.
+ *   9. best [1] (int64, needs cost): the row of the smallest cost among rows with verdict == 0 (and rtn >= 0 when rtn is
+ *      given); ties to the smaller index; rows whose cost is NaN are never chosen; -1 when there is none.
+ * Accuracy: a peak differs from the exact one by at most 24 u F, u = 2^-53, F = the item's expression at the
+ * end of its interval with every input replaced by its magnitude.  An output is computed only where its pointer is
+ * non-NULL.  DIRECT_ERR_INVALID, nothing launched: a NULL handle / struct / n_seg / T / status, a non-positive batch /
+ * n_seg_max, a bad mem, not exactly one of bez and poly, corridor pointers not all-or-none or p_max <= 0 with them, cpeak or
+ * c_where without a corridor, a NaN limit, a clearance that is negative or NaN, limit_on_norm not 0 or 1, best without cost.
+ * Host-memory calls stage every array through temporary device buffers and block; device-memory calls only enqueue on the
+ * handle's stream (no host synchronisation).  The per-segment partial results live in one workspace per handle: 136 bytes x
+ * batch x n_seg_max of device memory (16 doubles per segment slot and its start time; 446 MB for 32768 x 100), allocated by
+ * the first call of a size, kept for later calls and freed by direct_ddp_destroy only - a caller short of memory audits in
+ * slices of the batch (rows are independent; `best` is then the caller's minimum over the slices).  Each call waits for the
+ * previous call's kernels, also after direct_ddp_set_stream. */
+#define DIRECT_AUDIT_VEL 1
+#define DIRECT_AUDIT_ACC 2
+#define DIRECT_AUDIT_JERK 4
+#define DIRECT_AUDIT_CORRIDOR 8
+#define DIRECT_AUDIT_INVALID 256
+
+typedef struct {
+  int32_t batch, n_seg_max;
+  int32_t p_max;             /* planes per polytope the corridor arrays hold (their stride); unused without a corridor */
+  int32_t mem;               /* direct_mem_t: where every array of `in` and `out` lives */
+  const int32_t* n_seg;      /* [batch] */
+  const void* T;             /* [batch][n_seg_max] getPolyTime() */
+  const void* bez;           /* [batch][n_seg_max][18] or NULL } exactly one */
+  const void* poly;          /* [batch][n_seg_max][18] or NULL }            */
+  const int32_t* n_planes;   /* [batch][n_seg_max] or NULL */
+  const void* planes;        /* [batch][n_seg_max][p_max][4] or NULL */
+  double max_vel, max_acc, max_jerk;   /* <= 0: not judged */
+  double clearance;          /* >= 0: the corridor margin demanded (0: the curve may touch a plane) */
+  int32_t limit_on_norm;     /* 0: judge the per-axis peaks; 1: the Euclidean ones */
+  int32_t reserved;          /* 0 */
+  const void* cost;          /* [batch] Real or NULL */
+  const int32_t* rtn;        /* [batch] or NULL */
+} direct_audit_in_t;
+
+typedef struct {
+  int32_t* status;           /* [batch], required: 0 or -1 */
+  void* t_total;             /* [batch] or NULL */
+  void *vpeak, *apeak, *jpeak;   /* [batch] each, or NULL */
+  void *vnorm, *anorm, *jnorm;   /* [batch] each, or NULL */
+  void* cpeak;               /* [batch] or NULL */
+  int32_t* c_where;          /* [batch][2] or NULL */
+  void* at;                  /* [batch][4] or NULL */
+  void* seg_peak;            /* [batch][n_seg_max][4] or NULL */
+  void* gap;                 /* [batch][3] or NULL */
+  int32_t* verdict;          /* [batch] or NULL */
+  void* slowdown;            /* [batch] or NULL */
+  int64_t* best;             /* [1] or NULL */
+} direct_audit_out_t;
+
+direct_status_t direct_traj_audit_batch(direct_ddp_handle_t h, const direct_audit_in_t* in, direct_audit_out_t* out);
+/* HIP-event time of the last direct_traj_audit_batch kernels on the handle's stream [ms] */
+direct_status_t direct_traj_audit_last_ms(direct_ddp_handle_t h, float* ms);
+
 /* ---- stepwise interface (per-pass parity tests and profiling) ------------------------ */
 /* begin: setup + initialroll + mu/filter/reg reset (ddp_optimizer.cpp:42-286). */
 direct_status_t direct_ddp_begin(direct_ddp_handle_t h, const direct_ddp_params_t* params,
