@@ -17,9 +17,10 @@ class Config(C.Structure):
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
            "direct_cluster_polygon_generation_batch", "direct_cluster_convex_test", "direct_cluster_last_ms",
-           "direct_cluster_set_stream", "direct_cluster_hull_planes_batch")
+           "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
+GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
 _BOUND = False
 
 
@@ -39,6 +40,8 @@ def _lib():
         L.direct_cluster_set_stream.argtypes = [C.c_void_p, C.c_void_p]
         L.direct_cluster_hull_planes_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
                                                         C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
+        L.direct_cluster_grid_path_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                                      C.c_int32] + [C.c_void_p] * 6
         _BOUND = True
     return L
 
@@ -135,6 +138,25 @@ class ClusterGenerator:
         cut = lambda a, n, cap: [a[b, :min(int(n[b]), cap)].copy() for b in range(B)]
         return dict(planes=cut(pl, npl, plane_capacity), plane_int=cut(pi, npl, plane_capacity),
                     vertices=cut(vt, nv, vertex_capacity), center=ctr, degenerate=deg, n_planes=npl, n_vertices=nv, rtn=rtn)
+
+    def grid_paths(self, starts, goals, path_capacity=4096, max_rounds=0, want_dist=False):
+        """Optimal 26-connected voxel paths on the handle's map for a batch of (start, goal) voxel-index pairs
+        (direct_cluster_grid_path_batch; stands where the reference calls gridPathFinder::AstarSearch).  -> dict(paths: list
+        of [n][3] int32 arrays, start first (the first path_capacity voxels on GRID_PATH_OVERFLOW, empty without a path),
+        path_len, path_cost, rtn, stats [B][2] (rounds, tile visits), dist [B][X*Y*Z] float64 or None)"""
+        starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
+        goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+        assert starts.shape == goals.shape
+        B, cap = starts.shape[0], int(path_capacity)
+        xyz = np.zeros((B, cap, 3), np.int32)
+        n, rtn, stats = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2), np.int32)
+        cost = np.zeros(B, np.float64)
+        dist = np.zeros((B, int(np.prod(self.dims))), np.float64) if want_dist else None
+        _check(_lib().direct_cluster_grid_path_batch(self.h, B, starts.ctypes.data, goals.ctypes.data, cap, int(max_rounds),
+                                                     abi.MEM_HOST, xyz.ctypes.data, n.ctypes.data, cost.ctypes.data,
+                                                     dist.ctypes.data if want_dist else None, stats.ctypes.data, rtn.ctypes.data))
+        return dict(paths=[xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)], path_len=n, path_cost=cost, rtn=rtn, stats=stats,
+                    dist=dist)
 
     def set_stream(self, hip_stream):
         _check(_lib().direct_cluster_set_stream(self.h, C.c_void_p(hip_stream)))

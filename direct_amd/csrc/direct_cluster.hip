@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/direct_cluster.h"
+#include "grid_path_math.h"
 #include "hull_core.h"
 
 namespace {
@@ -976,6 +977,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 }
 
 #include "hull_kernels.h"
+#include "grid_path.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1009,6 +1011,10 @@ struct direct_cluster_handle_s {
   int resident_batch = 0;    // seeds of the last polygon_generation_batch whose clusters are still in D.cluster / D.el (0: none)
   void* hull_out = nullptr;  // device staging of its host outputs
   size_t hull_out_bytes = 0;
+  PathDev P = {};            // workspace of grid_path_batch, allocated by its first call (never shrunk, freed in destroy)
+  bool have_path = false;
+  void* path_out = nullptr;  // the read-back ring and the device staging of its host outputs, grown with path_capacity
+  size_t path_out_bytes = 0;
 };
 
 extern "C" {
@@ -1089,6 +1095,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->hull_out) (void)hipFree(h->hull_out);
+  if (h->path_out) (void)hipFree(h->path_out);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   delete h;
@@ -1352,6 +1359,110 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
   hipError_t e2 = hipStreamSynchronize(h->stream);
   if (e != hipSuccess || e2 != hipSuccess)
     return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_t batch, const int32_t* starts, const int32_t* goals,
+                                               int32_t path_capacity, int32_t max_rounds, int32_t mem, int32_t* path_xyz,
+                                               int32_t* path_len, double* path_cost, double* dist, int32_t* stats, int32_t* rtn) {
+  if (!h || !starts || !goals) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (batch <= 0 || batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
+  if (path_capacity <= 0 || max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  PathDev& P = h->P;
+  const size_t B = h->cfg.max_batch, nb = (size_t)batch;
+  if (!h->have_path) {  // all or nothing, as the hull's scratch
+    PathDev N = {};
+    N.X = D.max_x; N.Y = D.max_y; N.Z = D.max_z; N.YZ = D.max_yz; N.G = D.G;
+    N.tx = gp::tiles_along(N.X); N.ty = gp::tiles_along(N.Y); N.tz = gp::tiles_along(N.Z);
+    N.ntiles = N.tx * N.ty * N.tz;
+    N.map = h->map;
+    std::vector<void*> mine;
+    hipError_t ae = hipSuccess;
+    auto A = [&](auto pp, size_t bytes) {
+      if (ae != hipSuccess) return;
+      void* q = nullptr;
+      ae = hipMalloc(&q, bytes);
+      if (ae != hipSuccess) return;
+      mine.push_back(q);
+      *pp = (typename std::remove_pointer<decltype(pp)>::type)q;
+    };
+    A(&N.field, B * (size_t)N.G * sizeof(double));
+    A(&N.flag[0], B * (size_t)N.ntiles);
+    A(&N.flag[1], B * (size_t)N.ntiles);
+    A(&N.ends, B * 6 * sizeof(int));
+    A(&N.pending, B * sizeof(int));
+    A(&N.rounds, B * sizeof(int));
+    A(&N.visits, B * sizeof(int));
+    if (ae != hipSuccess) {
+      for (void* q : mine) (void)hipFree(q);
+      return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
+    }
+    h->allocs.insert(h->allocs.end(), mine.begin(), mine.end());
+    P = N;
+    h->have_path = true;
+  }
+  // one block for the read-back ring and the staging of host outputs (path_xyz, path_len, path_cost, stats, rtn)
+  const size_t cap = (size_t)path_capacity;
+  const size_t sz[6] = {nb * cap * sizeof(int), nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double),
+                        nb * 2 * sizeof(int32_t), nb * sizeof(int32_t)};
+  size_t off[6], total = 0;
+  for (int i = 0; i < 6; i++) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
+  if (total > h->path_out_bytes) {
+    if (h->path_out) {
+      CHIP_TRY(hipStreamSynchronize(h->stream));
+      (void)hipFree(h->path_out);
+      h->path_out = nullptr; h->path_out_bytes = 0;
+    }
+    CHIP_TRY(hipMalloc(&h->path_out, total));
+    h->path_out_bytes = total;
+  }
+  P.ring = (int*)h->path_out;
+  P.cap = (int)cap;
+  void* user[5] = {path_xyz, path_len, path_cost, stats, rtn};
+  void* dev[5];
+  for (int i = 0; i < 5; i++) dev[i] = mem == DIRECT_MEM_HOST ? (user[i] ? (char*)h->path_out + off[i + 1] : nullptr) : user[i];
+  std::vector<int> ends(nb * 6);
+  for (size_t b = 0; b < nb; b++)
+    for (int a = 0; a < 3; a++) { ends[6 * b + a] = starts[3 * b + a]; ends[6 * b + 3 + a] = goals[3 * b + a]; }
+  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
+  CHIP_TRY(hipGetLastError());
+  // Rounds are separate launches, enqueued blindly kRoundsPerCheck at a time (a workgroup whose tile is not active returns at
+  // once); then ONE read-back of the per-query "a tile was woken in round r" words says whether any query goes on.
+  constexpr int kRoundsPerCheck = 8;
+  const long long lim = max_rounds > 0 ? (long long)max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
+  std::vector<int> pending(nb);
+  int done = 0;
+  while (done < lim) {
+    const int n = (int)std::min<long long>(kRoundsPerCheck, lim - done);
+    for (int r = 0; r < n; r++) hipLaunchKernelGGL(k_path_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, done + r);
+    CHIP_TRY(hipGetLastError());
+    done += n;
+    CHIP_TRY(hipMemcpyAsync(pending.data(), P.pending, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CHIP_TRY(hipStreamSynchronize(h->stream));
+    bool live = false;
+    for (int v : pending) live |= v == done;
+    if (!live) break;
+  }
+  hipLaunchKernelGGL(k_path_trace, dim3(batch), dim3(64), 0, h->stream, P, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
+                     (int32_t*)dev[3], (int32_t*)dev[4]);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+  h->timed = e == hipSuccess;
+  if (mem == DIRECT_MEM_HOST)
+    for (int i = 0; i < 5 && e == hipSuccess; i++)
+      if (user[i]) e = hipMemcpyAsync(user[i], dev[i], sz[i + 1], hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && dist)
+    e = hipMemcpyAsync(dist, P.field, nb * (size_t)P.G * sizeof(double),
+                       mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
+  hipError_t e2 = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess || e2 != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   return DIRECT_OK;
 }
 

@@ -115,10 +115,56 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
                                                  double* vertices, int32_t* n_vertices, double* center, int32_t* degenerate,
                                                  int32_t* rtn);
 
+/* ---- grid paths: the stage in front of the corridor (map -> grid path -> corridor) -------------------------------
+ * Shortest 26-connected voxel paths for a BATCH of (start, goal) queries on the map of direct_cluster_set_map.  Stands where
+ * the reference calls gridPathFinder::AstarSearch (global_planner/src/utils/a_star.cpp:179-280, from
+ * teach_repeat_planner.cpp:163-169), on the reference's own graph with the reference's own cost arithmetic, but it returns
+ * the OPTIMAL path: the reference multiplies its heuristic by a tie_breaker > 1 and depends on its expansion order, so its
+ * path costs this much or more and is not reproduced.
+ *   Graph   the 26 neighbours of a voxel (a_star.cpp:224-234).  A move goes INTO a voxel that lies inside the map
+ *           (:236-240) and whose map byte is 0 (:242-246).  No corner-cutting rule, as in the reference.  The start
+ *           voxel's own byte is not looked at (the reference expands it regardless, :194-198).
+ *   Cost    d(start) = 0, d(v) = min over the neighbours u of fl(d(u) + w), w = sqrt(dx^2 + dy^2 + dz^2) in {1.0, sqrt(2.0),
+ *           sqrt(3.0)} as doubles, one rounded double addition per move: gScore's arithmetic (:252-254), folded from the
+ *           START.  This is the cost a heap Dijkstra (or an admissible A*) with the same additions returns, bit for bit.
+ *   Path    path_cost = d(goal).  The path is read backwards from the goal: the predecessor of v is the first neighbour u,
+ *           in ascending (dx, dy, dz) lexicographic order from (-1, -1, -1), that is in the graph and has
+ *           fl(d(u) + w) == d(v) as doubles.  It is emitted start first, goal last; the left-to-right double sum of its
+ *           step weights equals path_cost to the bit.
+ * starts / goals are HOST arrays [batch][3] of voxel indices; batch <= max_batch; path_capacity > 0 (it decides OVERFLOW
+ * whether path_xyz is asked for or not).  Outputs in memory kind `mem` (DIRECT_MEM_HOST or DIRECT_MEM_DEVICE; anything else is
+ * DIRECT_ERR_INVALID), any may be NULL:
+ *   path_xyz[batch][path_capacity][3], path_len[batch] (voxels on the path: the length NEEDED, also on overflow),
+ *   path_cost[batch], rtn[batch] (codes below, per query: other queries are unaffected),
+ *   dist[batch][max_x*max_y*max_z]  the field d: exact wherever the true distance is <= path_cost (for NO_PATH: the whole
+ *           connected component of the start); elsewhere any value >= the true distance, +inf included (the search is
+ *           pruned by the goal's current value).  Obstacle voxels hold +inf (an occupied start holds its 0).
+ *   stats[batch][2]  rounds in which the query had an active tile, tile visits: diagnostic, NOT deterministic.
+ * path_xyz, path_len, path_cost, rtn and dist where it is exact do not depend on the launch shape: one call of 64, two
+ * calls of 32 and a permuted batch give identical bytes.
+ * Method: a label-correcting relaxation over 8^3 tiles, one kernel launch per round; max_rounds bounds the rounds
+ * (0: the library's default, 2 * (number of tiles) + 64) and a query still changing then ends with ROUND_LIMIT.
+ * The call owns a workspace of its own, allocated by the first call, never shrunk and freed in direct_cluster_destroy:
+ * the field in double, 8 B x voxels x max_batch (0.82 GB at 64 x 1.6 M voxels), plus one activity byte per tile and query
+ * (twice) and 4 B x path_capacity per query for the read-back.  It does NOT invalidate the clusters a preceding
+ * direct_cluster_polygon_generation_batch left resident.  direct_cluster_last_ms covers it, direct_cluster_set_stream is
+ * honoured. */
+#define DIRECT_GRID_PATH_OK 0
+#define DIRECT_GRID_PATH_NO_PATH 1      /* goal occupied and != start, or not connected: path_len 0, path_cost +inf */
+#define DIRECT_GRID_PATH_BAD_ENDPOINT 2 /* start or goal outside the map: nothing is computed, path_len 0, path_cost NaN */
+#define DIRECT_GRID_PATH_OVERFLOW 3     /* path longer than path_capacity: path_len is the needed length, path_cost is valid, path_xyz holds the first path_capacity voxels */
+#define DIRECT_GRID_PATH_ROUND_LIMIT 4  /* max_rounds reached with tiles still active: no path (path_len 0, path_cost NaN); never a hang */
+/* start == goal is OK with length 1 and cost 0 (a_star.cpp:208-218), whatever the voxel's byte. */
+direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_t batch, const int32_t* starts,
+                                               const int32_t* goals, int32_t path_capacity, int32_t max_rounds, int32_t mem,
+                                               int32_t* path_xyz, int32_t* path_len, double* path_cost, double* dist,
+                                               int32_t* stats, int32_t* rtn);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
-/* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch call */
+/* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
+ * grid_path_batch call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
