@@ -207,7 +207,9 @@ __device__ void q_begin(const QBatch<St>& Q, QLds& L, int b, int lane) {
     xg[lane] = (double)Q.xg[(size_t)b * NX + lane];
     L.xn[lane] = (double)Q.x0[(size_t)b * NX + lane];
   }
-  if (lane < NU) L.un[lane] = lane == 0 ? Q.c.m * Q.c.g : 0.0;  // the hover input
+  // the hover input, rounded to the storage type before use like every later input: the roll and its cost belong to
+  // the U that is stored (float(m g) != m g; the next pass reads the stored value)
+  if (lane < NU) L.un[lane] = lane == 0 ? (double)(St)(Q.c.m * Q.c.g) : 0.0;
   QSYNC();
   double cost = 0.0;
   St* X = Q.X[0] + (size_t)b * (N + 1) * NX;

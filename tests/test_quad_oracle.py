@@ -59,3 +59,26 @@ def test_ilqr_reaches_the_goal_with_monotone_cost():
         assert np.linalg.norm(g["x"][-1, :3] - xg[b, :3]) < 0.15 and np.abs(g["x"][-1, 3:6]).max() < 0.2
         assert g["iter"] < 50 and np.abs(g["x"][:, 6:8]).max() < 1.2   # tilts, never near the Euler singularity
         s.close()
+
+
+def test_jacobians_match_finite_differences_at_general_states():
+    """three distinct inertia entries (with J[0] == J[1] the (J1 - J0) terms of the last row are multiplied by zero), yaw
+    anywhere in +-6 rad, body rates of order 1"""
+    p = params(inertia=(C.c_double * 3)(2.64e-3, 3.71e-3, 4.96e-3))
+    rng = np.random.default_rng(1)
+    for _ in range(8):
+        x = rng.normal(0, 0.4, 12)
+        x[8] = rng.uniform(-6, 6)
+        x[9:] = rng.normal(0, 1.0, 3)
+        u = np.array([9.0, 0.01, -0.02, 0.005]) + rng.normal(0, 0.01, 4)
+        A, B = quadapi.jacobians(p, x, u)
+        h = 1e-6
+        for j in range(12):
+            e = np.zeros(12); e[j] = h
+            fd = (quadapi.step(p, x + e, u) - quadapi.step(p, x - e, u)) / (2 * h)
+            assert np.abs(fd - A[:, j]).max() < 1e-8
+        for j in range(4):
+            e = np.zeros(4); e[j] = h
+            fd = (quadapi.step(p, x, u + e) - quadapi.step(p, x, u - e)) / (2 * h)
+            assert np.abs(fd - B[:, j]).max() < 1e-7
+        assert A[11, 9] != 0 and A[11, 10] != 0               # the entries the default inertia zeroes
