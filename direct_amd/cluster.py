@@ -15,12 +15,21 @@ class Config(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class MapCloud(C.Structure):  # direct_map_cloud_t
+    _fields_ = [("map_lower", C.c_double * 3), ("map_upper", C.c_double * 3), ("resolution", C.c_double),
+                ("cloud_margin", C.c_double), ("border", C.c_int32), ("mode", C.c_int32), ("stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
            "direct_cluster_polygon_generation_batch", "direct_cluster_convex_test", "direct_cluster_last_ms",
-           "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch")
+           "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
+           "direct_cluster_map_from_cloud", "direct_cluster_get_map")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
+MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
+MAP_REPLACE, MAP_ADD = 0, 1
 _BOUND = False
 
 
@@ -42,6 +51,8 @@ def _lib():
                                                         C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8
         L.direct_cluster_grid_path_batch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                                       C.c_int32] + [C.c_void_p] * 6
+        L.direct_cluster_map_from_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.direct_cluster_get_map.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _BOUND = True
     return L
 
@@ -75,6 +86,39 @@ class ClusterGenerator:
         g = np.ascontiguousarray(grid, np.uint8)
         assert g.shape == self.dims
         _check(_lib().direct_cluster_set_map(self.h, abi.MEM_HOST, g.ctypes.data))
+
+    def set_map_from_cloud(self, points, map_lower, resolution, cloud_margin=0.25, map_upper=None, border="clamp", add=False):
+        """The map from a point cloud, on the device (direct_cluster_map_from_cloud; stands where the reference runs
+        rcvPointCloudCallBack, teach_repeat_planner.cpp:523-581).  points: a NumPy array or a device tensor of shape [n, 3] or
+        [n, 4] (a pcl::PointXYZ buffer), float32.  border: "clamp" (the polytope generator's map) or "drop" (the path finder's;
+        map_upper defaults to map_lower + dims * resolution).  add: keep the map the handle holds.
+        -> dict(points, skipped_nonfinite, dropped, occupied)"""
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        upper = lower + np.asarray(self.dims, np.float64) * float(resolution) if map_upper is None else np.asarray(map_upper, np.float64).reshape(3)
+        par = MapCloud((C.c_double * 3)(*lower), (C.c_double * 3)(*upper), float(resolution), float(cloud_margin),
+                       {"clamp": MAP_BORDER_CLAMP, "drop": MAP_BORDER_DROP}[border], MAP_ADD if add else MAP_REPLACE, 0, 0)
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            pts = np.ascontiguousarray(points, np.float32)
+            pts = pts.reshape(0, 3) if pts.size == 0 and pts.ndim != 2 else pts
+            mem, ptr = abi.MEM_HOST, pts.ctypes.data
+        else:
+            import torch
+            pts = points.to(torch.float32).contiguous()
+            assert pts.is_cuda
+            torch.cuda.current_stream(pts.device).synchronize()  # the handle's stream is not torch's
+            mem, ptr = abi.MEM_DEVICE, pts.data_ptr()
+        assert pts.ndim == 2 and pts.shape[1] in (3, 4), "points must have shape [n, 3] or [n, 4]"
+        par.stride = int(pts.shape[1])
+        n = int(pts.shape[0])
+        stats = np.zeros(4, np.int64)
+        _check(_lib().direct_cluster_map_from_cloud(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
+        return dict(points=int(stats[0]), skipped_nonfinite=int(stats[1]), dropped=int(stats[2]), occupied=int(stats[3]))
+
+    def get_map(self):
+        """The handle's map as a uint8 array of shape dims (direct_cluster_get_map)"""
+        g = np.zeros(self.dims, np.uint8)
+        _check(_lib().direct_cluster_get_map(self.h, abi.MEM_HOST, g.ctypes.data))
+        return g
 
     def polygon_generation(self, seeds, itr_inflate_max=1000, itr_cluster_max=50, fetch_clusters=True):
         """-> dict(vertex_idx [B][24], clusters: list of [n][3] arrays, cluster_num, iters, rtn).  fetch_clusters=False:

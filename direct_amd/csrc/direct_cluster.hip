@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -978,6 +979,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 
 #include "hull_kernels.h"
 #include "grid_path.h"
+#include "map_cloud.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1015,7 +1017,21 @@ struct direct_cluster_handle_s {
   bool have_path = false;
   void* path_out = nullptr;  // the read-back ring and the device staging of its host outputs, grown with path_capacity
   size_t path_out_bytes = 0;
+  float* cloud_in = nullptr;  // device staging of a host cloud of map_from_cloud, grown on demand
+  size_t cloud_in_bytes = 0;
+  unsigned long long* cloud_cnt = nullptr;  // [2] its counters
 };
+
+namespace {
+// The obstacles' summed-area table for k_convex's box test, from the map resident in h->map: the ONE place that builds it
+// (direct_cluster_set_map and direct_cluster_map_from_cloud both end here).  Enqueues only.
+hipError_t rebuild_sat(direct_cluster_handle_t h) {
+  const Dev& D = h->D;
+  hipLaunchKernelGGL(k_sat_fill, dim3(1024), dim3(256), 0, h->stream, D);
+  for (int axis = 2; axis >= 0; axis--) hipLaunchKernelGGL(k_sat_scan, dim3(256), dim3(256), 0, h->stream, D, axis);
+  return hipGetLastError();
+}
+}  // namespace
 
 extern "C" {
 
@@ -1096,6 +1112,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   for (void* p : h->allocs) (void)hipFree(p);
   if (h->hull_out) (void)hipFree(h->hull_out);
   if (h->path_out) (void)hipFree(h->path_out);
+  if (h->cloud_in) (void)hipFree(h->cloud_in);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   delete h;
@@ -1108,14 +1125,94 @@ direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, c
   CHIP_TRY(hipMemcpyAsync(h->map, map_data, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                           h->stream));
   CHIP_TRY(hipStreamSynchronize(h->stream));
-  {  // the obstacles' summed-area table for k_convex's box test
-    const Dev& D = h->D;
-    hipLaunchKernelGGL(k_sat_fill, dim3(1024), dim3(256), 0, h->stream, D);
-    for (int axis = 2; axis >= 0; axis--) hipLaunchKernelGGL(k_sat_scan, dim3(256), dim3(256), 0, h->stream, D, axis);
-    CHIP_TRY(hipGetLastError());
-    CHIP_TRY(hipStreamSynchronize(h->stream));
+  CHIP_TRY(rebuild_sat(h));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
+  h->have_map = true;
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const direct_map_cloud_t* p, int64_t n_points, int32_t mem,
+                                              const float* xyz, int64_t* stats) {
+  if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  if (!std::isfinite(p->cloud_margin) || !(p->cloud_margin >= 0.0)) return cfail(DIRECT_ERR_INVALID, "cloud_margin must be finite and not negative");
+  if (p->stride != 3 && p->stride != 4) return cfail(DIRECT_ERR_INVALID, "stride must be 3 or 4 floats per point");
+  if (p->border != DIRECT_MAP_BORDER_CLAMP && p->border != DIRECT_MAP_BORDER_DROP) return cfail(DIRECT_ERR_INVALID, "unknown border convention");
+  if (p->mode != DIRECT_MAP_REPLACE && p->mode != DIRECT_MAP_ADD) return cfail(DIRECT_ERR_INVALID, "unknown mode");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(p->map_lower[a]) || (p->border == DIRECT_MAP_BORDER_DROP && !std::isfinite(p->map_upper[a])))
+      return cfail(DIRECT_ERR_INVALID, "map_lower / map_upper must be finite");
+  const double inv = 1.0 / p->resolution;
+  if (!(p->cloud_margin * inv < (double)mc::kMaxSteps + 0.5)) return cfail(DIRECT_ERR_UNSUPPORTED, "cloud_margin above 1024 voxel steps");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  CloudDev C = {};
+  for (int a = 0; a < 3; a++) { C.lower[a] = p->map_lower[a]; C.upper[a] = p->map_upper[a]; }
+  C.resolution = p->resolution; C.inv = inv;
+  C.size[0] = D.max_x; C.size[1] = D.max_y; C.size[2] = D.max_z;
+  mc::inf_steps(p->cloud_margin, p->resolution, &C.s, &C.sz);
+  C.border = p->border; C.stride = p->stride; C.n = n_points; C.map = h->map;
+  if (!h->cloud_cnt) {
+    void* q = nullptr;
+    CHIP_TRY(hipMalloc(&q, 2 * sizeof(unsigned long long)));
+    h->allocs.push_back(q);
+    h->cloud_cnt = (unsigned long long*)q;
+  }
+  C.cnt = h->cloud_cnt;
+  const size_t bytes = (size_t)n_points * p->stride * sizeof(float);
+  if (mem == DIRECT_MEM_HOST && n_points > 0) {
+    if (bytes > h->cloud_in_bytes) {
+      if (h->cloud_in) {
+        CHIP_TRY(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->cloud_in);
+        h->cloud_in = nullptr; h->cloud_in_bytes = 0;
+      }
+      CHIP_TRY(hipMalloc((void**)&h->cloud_in, bytes));
+      h->cloud_in_bytes = bytes;
+    }
+    CHIP_TRY(hipMemcpyAsync(h->cloud_in, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+    C.xyz = h->cloud_in;
+  } else {
+    C.xyz = xyz;
+  }
+  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  hipError_t e = hipMemsetAsync(h->cloud_cnt, 0, 2 * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess && (p->mode == DIRECT_MAP_REPLACE || !h->have_map)) e = hipMemsetAsync(h->map, 0, (size_t)D.G, h->stream);
+  if (e == hipSuccess && n_points > 0) {
+    const long long lanes = (long long)n_points * (2 * C.s + 1) * (2 * C.s + 1);
+    const int blocks = (int)std::min<long long>((lanes + 255) / 256, 1 << 16);  // grid-stride beyond 16.8 M lanes
+    hipLaunchKernelGGL(k_cloud_raster, dim3(blocks), dim3(256), 0, h->stream, C);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = rebuild_sat(h);
+  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+  h->timed = e == hipSuccess;
+  unsigned long long cnt[2] = {0, 0};
+  int occupied = 0;  // the table's last entry is the sum over the whole map: the count and the table cannot disagree
+  if (e == hipSuccess && stats) e = hipMemcpyAsync(cnt, h->cloud_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && stats)
+    e = hipMemcpyAsync(&occupied, D.sat + ((size_t)(D.max_x + 1) * D.sat_yz - 1), sizeof(int), hipMemcpyDeviceToHost, h->stream);
+  hipError_t e2 = hipStreamSynchronize(h->stream);
+  // the map has been touched: whatever happened, an earlier table no longer describes it
+  if (e != hipSuccess || e2 != hipSuccess) {
+    h->have_map = false;
+    return cfail(DIRECT_ERR_DEVICE, std::string("map_from_cloud: ") + hipGetErrorString(e != hipSuccess ? e : e2));
   }
   h->have_map = true;
+  if (stats) { stats[0] = n_points; stats[1] = (int64_t)cnt[0]; stats[2] = (int64_t)cnt[1]; stats[3] = occupied; }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, uint8_t* map_data) {
+  if (!h || !map_data) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  CHIP_TRY(hipMemcpyAsync(map_data, h->map, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                          h->stream));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
   return DIRECT_OK;
 }
 

@@ -50,6 +50,27 @@ class polyhedronGenerator {
     if (direct_cluster_set_map(h_, DIRECT_MEM_HOST, map_data) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
     has_map_ = true;
   }
+  // the same grid from the sensor's points, built on the device: what rcvPointCloudCallBack does for this class
+  // (teach_repeat_planner.cpp:523-581: every point shifted by the box of voxel steps of cloud_margin, setObs(coord2gridIndex(...)),
+  // i.e. the CLAMPING border convention).  xyz[n][stride] host floats, stride 3 or 4 (a pcl::PointXYZ buffer); add = false is
+  // mapClear first.  Returns the number of occupied voxels.
+  int64_t setCloud(const float* xyz, int64_t n, int stride, double cloud_margin, bool add = false) {
+    direct_map_cloud_t p{};
+    for (int a = 0; a < 3; a++) {
+      p.map_lower[a] = lower_[a];
+      p.map_upper[a] = lower_[a] + (a == 0 ? mx_ : (a == 1 ? my_ : mz_)) * res_;
+    }
+    p.resolution = res_;
+    p.cloud_margin = cloud_margin;
+    p.border = DIRECT_MAP_BORDER_CLAMP;
+    p.mode = add ? DIRECT_MAP_ADD : DIRECT_MAP_REPLACE;
+    p.stride = stride;
+    int64_t stats[4];
+    if (direct_cluster_map_from_cloud(h_, &p, n, DIRECT_MEM_HOST, xyz, stats) != DIRECT_OK)
+      throw std::runtime_error(direct_cluster_last_error());
+    has_map_ = true;
+    return stats[3];
+  }
 
   std::array<int, 3> coord2Index(const std::array<double, 3>& c) const {  // :10-18
     auto f = [&](double v, double lo, int mx) {

@@ -194,3 +194,49 @@ def make_voxel_map(dims=(120, 120, 24), seed=7, n_pillars=60, n_boxes=25, n_ring
     free = np.argwhere(g == 0)
     seeds = free[rng.choice(len(free), 256, replace=False)].astype(np.int32)
     return g, seeds
+
+
+def make_point_cloud(dims, resolution, map_lower, seed=7, n_pillars=None, n_rings=None, on_lattice=0.5, outside=0.01, n_points=None):
+    """Synthetic float32 point cloud [n, 3] for ClusterGenerator.set_map_from_cloud: our own scene of pillars and vertical rings
+    (in the spirit of the reference's random map publisher, as make_voxel_map) inside the map dims * resolution from map_lower.
+    A pillar is sampled on a lattice of the map's resolution over its footprint and height; a ring is sampled along its
+    circle at half a voxel's spacing.  The fraction `on_lattice` of the objects is placed with its samples ON the voxel lattice
+    (coordinates map_lower + i * resolution rounded to float32: the faces between voxels, where the reference's
+    coordinate-wise inflation and a voxel-wise dilation part ways); the others are shifted by a random fraction of a voxel.
+    The fraction `outside` of the points is pushed up to three voxels beyond a face of the map.  n_points: the SAME scene seen
+    that many times, as a sensor that sweeps it repeatedly sees it - samples drawn with replacement, those of the off-lattice
+    objects moved by up to half a voxel each way - so that the occupied share of the map does not grow with the cloud."""
+    rng = _rng(seed, 0)
+    dims = np.asarray(dims, np.int64)
+    lower = np.asarray(map_lower, np.float64)
+    X, Y, Z = (int(d) for d in dims)
+    n_pillars = max(4, X * Y // 240) if n_pillars is None else n_pillars
+    n_rings = max(2, X * Y // 1200) if n_rings is None else n_rings
+    parts, lattice = [], []  # per object: its samples in voxel units, and whether they sit on the lattice
+    for _ in range(n_pillars):
+        w, hgt = int(rng.integers(1, 4)), int(rng.integers(max(1, Z // 3), Z + 1))
+        x0, y0 = int(rng.integers(1, max(2, X - w - 1))), int(rng.integers(1, max(2, Y - w - 1)))
+        i, j, k = np.meshgrid(np.arange(x0, x0 + w + 1), np.arange(y0, y0 + w + 1), np.arange(0, hgt + 1), indexing="ij")
+        p = np.stack([i.ravel(), j.ravel(), k.ravel()], axis=1).astype(np.float64)
+        lattice.append(rng.random() < on_lattice)
+        parts.append(p if lattice[-1] else p + rng.random(3))
+    for _ in range(n_rings):  # vertical rings in a plane x = const around a free hole
+        r = float(rng.uniform(3.0, 6.0))
+        c = np.array([rng.integers(2, max(3, X - 2)), rng.uniform(r + 1, max(r + 2, Y - r - 1)), rng.uniform(r, max(r + 1, Z - r))])
+        th = np.arange(0.0, 2 * np.pi, 0.5 / r)
+        for dx in (0.0, 1.0):
+            p = np.stack([np.full_like(th, c[0] + dx), c[1] + r * np.cos(th), c[2] + r * np.sin(th)], axis=1)
+            lattice.append(rng.random() < on_lattice)  # a ring's x is on the lattice or off it; y and z follow the circle
+            if not lattice[-1]:
+                p[:, 0] += rng.random()
+            parts.append(p)
+    p = np.concatenate(parts)
+    if n_points is not None:
+        on = np.concatenate([np.full(len(q), f) for q, f in zip(parts, lattice)])
+        pick = rng.integers(0, len(p), int(n_points))
+        p = p[pick] + np.where(on[pick, None], 0.0, rng.uniform(-0.5, 0.5, (int(n_points), 3)))
+    out = rng.random(len(p)) < outside
+    axis, side = rng.integers(0, 3, len(p)), rng.integers(0, 2, len(p))
+    far = np.where(side == 1, dims[axis] + rng.uniform(0.0, 3.0, len(p)), -rng.uniform(0.0, 3.0, len(p)))
+    p[out, axis[out]] = far[out]
+    return np.ascontiguousarray((p * float(resolution) + lower).astype(np.float32))

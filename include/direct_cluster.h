@@ -49,6 +49,56 @@ const char* direct_cluster_last_error(void);
  * map_data[max_x*max_y*max_z] in memory kind `mem`. */
 direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, const uint8_t* map_data);
 
+/* ---- the map from a point cloud: the stage in front of everything (cloud -> map -> grid path -> corridor) ----------
+ * Builds the resident map from the points a sensor delivers, where the reference runs rcvPointCloudCallBack
+ * (global_planner/src/teach_repeat_planner.cpp:523-581, "TRP") on one thread.  The map is the reference's, bit for bit:
+ *   Steps      s = (int)round(cloud_margin * inv), inv = 1.0 / resolution computed once (TRP:537, 1201), in x and y;
+ *              s_z = max(1, s / 2) in integer division in z (TRP:538).  cloud_margin = 0.0, the shipped launch file's
+ *              map_margin (global_planner.launch:34), still inflates by one voxel up and down in z.
+ *   Inflation  acts on COORDINATES, not on voxels: for every point and every offset (kx, ky, kz) of the
+ *              (2s+1)^2 x (2s_z+1) box the coordinate (double)p + (double)k * resolution is formed per axis (TRP:548-550:
+ *              p a float promoted to double, two roundings, no fused multiply-add) and quantised as
+ *              int((coord - lower) * inv).  A float32 point on a voxel face can land in either neighbour after the shift;
+ *              this is NOT "the point's voxel dilated by a box".
+ *   Border     the reference keeps two maps that disagree there:
+ *              DIRECT_MAP_BORDER_CLAMP  the polytope generator's: setObs(coord2gridIndex(coord)) (TRP:553, 557;
+ *                utils/a_star.h:141-149), index min(max(int(q), 0), size - 1) per axis: a point outside the map marks
+ *                border voxels.  This is the map polygon_generation_batch / hull_planes_batch stand on in the reference.
+ *              DIRECT_MAP_BORDER_DROP   the path finder's: setObs(x, y, z) (TRP:556; utils/a_star.cpp:74-85) discards a
+ *                coordinate outside [map_lower, map_upper) along any axis.  This is the map AstarSearch runs on.
+ *   Defined here, undefined in the reference:
+ *              (1) int(double) of a NaN or an out-of-range value: a point with ANY non-finite coordinate contributes
+ *                  nothing and is counted in stats[1]; a finite coordinate far outside is compared against the range before
+ *                  any conversion (CLAMP: the border voxel; DROP: discarded).
+ *              (2) in the path finder's setObs a coordinate in [size * resolution + map_lower, map_upper) passes the range
+ *                  test and indexes one past the array (49.95 .. 50 at the launch file's values): DROPPED here.
+ * The bytes written are 1; every writer of a voxel writes the same byte, so the map depends neither on the order of the
+ * points nor on the launch shape.  The summed-area table of the obstacles is rebuilt by the same code as in
+ * direct_cluster_set_map, and the call has set_map's effect on everything else the handle holds (resident clusters stay).
+ * xyz[n_points][stride] floats in memory kind `mem` (DIRECT_MEM_HOST or DIRECT_MEM_DEVICE); the map's size in voxels is the
+ * handle's.  stats (host, may be NULL): [0] points read, [1] points skipped as non-finite, [2] (point, offset) triples
+ * dropped by BORDER_DROP (0 under CLAMP), [3] voxels with byte 1 after the call.
+ * DIRECT_ERR_INVALID: null handle or parameters; n_points < 0; xyz == NULL with n_points > 0; resolution <= 0 or not
+ * finite; cloud_margin < 0 or not finite; map_lower (and map_upper under DROP) not finite; stride other than 3 or 4; unknown
+ * border, mode or mem.  DIRECT_ERR_UNSUPPORTED: s above 1024.  n_points == 0 with REPLACE gives an empty map, which IS a map.
+ * Runs on the handle's stream and synchronises before it returns; direct_cluster_last_ms covers the clear, the kernel and
+ * the table (not the copy of a host cloud). */
+#define DIRECT_MAP_BORDER_CLAMP 0  /* the polytope generator's map: coord2gridIndex clamps (TRP:553, 557) */
+#define DIRECT_MAP_BORDER_DROP  1  /* the path finder's map: setObs(x, y, z) discards (a_star.cpp:74-85) */
+#define DIRECT_MAP_REPLACE 0       /* mapClear first */
+#define DIRECT_MAP_ADD     1       /* keep what the handle holds; a handle without a map starts empty, as after paramSet */
+typedef struct {
+  double map_lower[3], map_upper[3];   /* map_upper is read by BORDER_DROP only */
+  double resolution, cloud_margin;
+  int32_t border, mode;
+  int32_t stride;                      /* floats per point: 3, or 4 for a pcl::PointXYZ buffer as it lies in memory */
+  int32_t reserved;
+} direct_map_cloud_t;
+direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const direct_map_cloud_t* p, int64_t n_points,
+                                              int32_t mem, const float* xyz, int64_t* stats /* host [4], may be NULL */);
+/* The handle's map, map_data[max_x*max_y*max_z] in memory kind `mem`; DIRECT_ERR_INVALID without a map. */
+direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, uint8_t* map_data);
+
 /* Return codes per seed (the reference has none: it writes past its buffers instead). */
 #define DIRECT_CLUSTER_OK 0
 #define DIRECT_CLUSTER_OVERFLOW 1  /* cluster_capacity / candidate_capacity exceeded: result truncated, not usable */
@@ -164,7 +214,7 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
- * grid_path_batch call */
+ * grid_path_batch / map_from_cloud call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
