@@ -21,15 +21,27 @@ class MapCloud(C.Structure):  # direct_map_cloud_t
                 ("reserved", C.c_int32)]
 
 
+class PlanCheckIn(C.Structure):  # direct_plan_check_in_t
+    _fields_ = [("batch", C.c_int32), ("n_seg_max", C.c_int32), ("mem", C.c_int32), ("dtype", C.c_int32), ("n_seg", C.c_void_p),
+                ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p), ("map_lower", C.c_double * 3), ("resolution", C.c_double),
+                ("margin", C.c_double), ("depth", C.c_int32), ("outside_blocks", C.c_int32), ("t_from", C.c_void_p)]
+
+
+class PlanCheckOut(C.Structure):  # direct_plan_check_out_t
+    _fields_ = [("status", C.c_void_p), ("verdict", C.c_void_p), ("t_free", C.c_void_p), ("first", C.c_void_p),
+                ("hit_box", C.c_void_p), ("seg_first", C.c_void_p), ("stats", C.c_void_p)]
+
+
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
            "direct_cluster_polygon_generation_batch", "direct_cluster_convex_test", "direct_cluster_last_ms",
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
-           "direct_cluster_map_from_cloud", "direct_cluster_get_map")
+           "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
 MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
+PLAN_CHECK_INVALID = -1
 _BOUND = False
 
 
@@ -53,6 +65,7 @@ def _lib():
                                                       C.c_int32] + [C.c_void_p] * 6
         L.direct_cluster_map_from_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.direct_cluster_get_map.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_plan_check_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -201,6 +214,57 @@ class ClusterGenerator:
                                                      dist.ctypes.data if want_dist else None, stats.ctypes.data, rtn.ctypes.data))
         return dict(paths=[xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)], path_len=n, path_cost=cost, rtn=rtn, stats=stats,
                     dist=dist)
+
+    def check_plans(self, n_seg, T, map_lower, resolution, bez=None, poly=None, depth=8, margin=0.0, t_from=None, outside_blocks=False, count=False):
+        """Solved plans against the map the handle holds now (direct_cluster_plan_check_batch): for every plan whether the curve
+        from t_from on is certified clear of occupied voxels, and otherwise the start time t_free of the first piece (of duration
+        T_i / 2^depth) whose bounding box touches one - conservative: such a box need not mean that the curve enters the voxel.
+        n_seg [B] int32, T [B][N], exactly one of bez / poly [B][N][18] (float32 or float64, one type for all three), t_from [B]
+        float64 or None: NumPy arrays, or device tensors (then every output is a device tensor too).
+        -> dict(status, verdict, t_free, first [B][2], hit_box [B][6], seg_first [B][N]); count=True adds the diagnostics unresolved
+        (segment slots the first pass left to the deep pass) and box_tests, at the price of one atomic add per wave."""
+        assert (bez is None) != (poly is None), "exactly one of bez and poly"
+        coef = bez if poly is None else poly
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        par = PlanCheckIn(depth=int(depth), outside_blocks=int(bool(outside_blocks)), resolution=float(resolution), margin=float(margin),
+                          map_lower=(C.c_double * 3)(*lower))
+        stats = np.zeros(2, np.int64)
+        if isinstance(T, np.ndarray) or not hasattr(T, "data_ptr"):
+            T = np.asarray(T)
+            real = np.float32 if T.dtype == np.float32 else np.float64
+            T, coef = np.ascontiguousarray(T, real), np.ascontiguousarray(coef, real)
+            n_seg = np.ascontiguousarray(n_seg, np.int32)
+            B, N = T.shape
+            tf = None if t_from is None else np.ascontiguousarray(t_from, np.float64)
+            out = dict(status=np.zeros(B, np.int32), verdict=np.zeros(B, np.int32), t_free=np.zeros(B, np.float64),
+                       first=np.zeros((B, 2), np.int32), hit_box=np.zeros((B, 6), np.int32), seg_first=np.zeros((B, N), np.int32))
+            ptr = lambda a: a.ctypes.data
+            par.mem, par.dtype = abi.MEM_HOST, abi.F32 if real == np.float32 else abi.F64
+        else:
+            import torch
+            real = torch.float32 if T.dtype == torch.float32 else torch.float64
+            T, coef = T.to(real).contiguous(), coef.to(real).contiguous()
+            n_seg = n_seg.to(torch.int32).contiguous()
+            assert T.is_cuda and coef.is_cuda and n_seg.is_cuda
+            B, N = T.shape
+            tf = None if t_from is None else t_from.to(torch.float64).contiguous()
+            mk = lambda shape, dt, fill=0: torch.full(shape, fill, dtype=dt, device=T.device)
+            out = dict(status=mk((B,), torch.int32), verdict=mk((B,), torch.int32), t_free=mk((B,), torch.float64),
+                       first=mk((B, 2), torch.int32), hit_box=mk((B, 6), torch.int32), seg_first=mk((B, N), torch.int32, -1))
+            torch.cuda.current_stream(T.device).synchronize()  # the handle's stream is not torch's
+            ptr = lambda a: a.data_ptr()
+            par.mem, par.dtype = abi.MEM_DEVICE, abi.F32 if real == torch.float32 else abi.F64
+        assert tuple(coef.shape) == (B, N, 18) and tuple(n_seg.shape) == (B,) and (tf is None or tuple(tf.shape) == (B,))
+        par.batch, par.n_seg_max = B, N
+        par.n_seg, par.T = ptr(n_seg), ptr(T)
+        par.bez, par.poly = (ptr(coef), None) if poly is None else (None, ptr(coef))
+        par.t_from = None if tf is None else ptr(tf)
+        o = PlanCheckOut(*[ptr(out[k]) for k in ("status", "verdict", "t_free", "first", "hit_box", "seg_first")],
+                         stats.ctypes.data if count else None)
+        _check(_lib().direct_cluster_plan_check_batch(self.h, C.addressof(par), C.addressof(o)))
+        if count:
+            out.update(unresolved=int(stats[0]), box_tests=int(stats[1]))
+        return out
 
     def set_stream(self, hip_stream):
         _check(_lib().direct_cluster_set_stream(self.h, C.c_void_p(hip_stream)))

@@ -980,6 +980,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "hull_kernels.h"
 #include "grid_path.h"
 #include "map_cloud.h"
+#include "plan_check.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1020,6 +1021,10 @@ struct direct_cluster_handle_s {
   float* cloud_in = nullptr;  // device staging of a host cloud of map_from_cloud, grown on demand
   size_t cloud_in_bytes = 0;
   unsigned long long* cloud_cnt = nullptr;  // [2] its counters
+  void* plan_ws = nullptr;    // workspace of plan_check_batch (counters, start times, per-slot leaves, unresolved list), grown on demand
+  size_t plan_ws_bytes = 0;
+  void* plan_io = nullptr;    // device staging of its host arrays, grown on demand
+  size_t plan_io_bytes = 0;
 };
 
 namespace {
@@ -1113,6 +1118,8 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   if (h->hull_out) (void)hipFree(h->hull_out);
   if (h->path_out) (void)hipFree(h->path_out);
   if (h->cloud_in) (void)hipFree(h->cloud_in);
+  if (h->plan_ws) (void)hipFree(h->plan_ws);
+  if (h->plan_io) (void)hipFree(h->plan_io);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   delete h;
@@ -1560,6 +1567,96 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
   hipError_t e2 = hipStreamSynchronize(h->stream);
   if (e != hipSuccess || e2 != hipSuccess)
     return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  return DIRECT_OK;
+}
+
+namespace {
+// one device block of at least `bytes`, kept in the handle and regrown (after the stream has drained) when a call needs more
+hipError_t plan_grow(direct_cluster_handle_t h, void** buf, size_t* have, size_t bytes) {
+  if (bytes <= *have) return hipSuccess;
+  if (*buf) {
+    hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return e;
+    (void)hipFree(*buf);
+    *buf = nullptr; *have = 0;
+  }
+  hipError_t e = hipMalloc(buf, bytes);
+  if (e == hipSuccess) *have = bytes;
+  return e;
+}
+}  // namespace
+
+direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in, direct_plan_check_out_t* out) {
+  if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->n_seg_max <= 0) return cfail(DIRECT_ERR_INVALID, "batch and n_seg_max must be positive");
+  if ((in->bez != nullptr) == (in->poly != nullptr)) return cfail(DIRECT_ERR_INVALID, "exactly one of bez and poly");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "dtype is neither DIRECT_F32 nor DIRECT_F64");
+  if (in->depth < 0 || in->depth > pk::kMaxDepth) return cfail(DIRECT_ERR_INVALID, "depth outside [0, 12]");
+  if (in->outside_blocks != 0 && in->outside_blocks != 1) return cfail(DIRECT_ERR_INVALID, "outside_blocks is neither 0 nor 1");
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  if (!std::isfinite(in->margin) || !(in->margin >= 0.0)) return cfail(DIRECT_ERR_INVALID, "margin must be finite and not negative");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  const size_t B = (size_t)in->batch, nm = (size_t)in->n_seg_max, slots = B * nm;
+  if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  const bool host = in->mem == DIRECT_MEM_HOST;
+  const size_t r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  // workspace: counters, S, per-slot leaves, unresolved list
+  const size_t w_S = up(256), w_first = w_S + up(B * (nm + 1) * sizeof(double)), w_list = w_first + up(slots * sizeof(int)),
+               w_total = w_list + up(slots * sizeof(int));
+  CHIP_TRY(plan_grow(h, &h->plan_ws, &h->plan_ws_bytes, w_total));
+  PlanDev A = {};
+  for (int a = 0; a < 3; a++) A.G.lower[a] = in->map_lower[a];
+  A.G.inv = 1.0 / in->resolution;
+  A.G.margin = in->margin;
+  A.G.size[0] = D.max_x; A.G.size[1] = D.max_y; A.G.size[2] = D.max_z;
+  A.G.outside_blocks = in->outside_blocks;
+  A.batch = in->batch; A.nmax = in->n_seg_max; A.depth = in->depth; A.poly = in->poly != nullptr; A.has_from = in->t_from != nullptr;
+  A.count = out->stats != nullptr;
+  char* W = (char*)h->plan_ws;
+  A.n_list = (unsigned*)W; A.n_tests = (unsigned long long*)(W + 8);
+  A.S = (double*)(W + w_S); A.ws_first = (int*)(W + w_first); A.list = (int*)(W + w_list);
+  const void* coef = in->poly ? in->poly : in->bez;
+  // host arrays go through one staging block: n_seg, T, coef, t_from in; the six outputs back
+  const void* src[4] = {in->n_seg, in->T, coef, in->t_from};
+  void* user[6] = {out->status, out->verdict, out->t_free, out->first, out->hit_box, out->seg_first};
+  const size_t isz[4] = {B * 4, slots * r, slots * 18 * r, B * 8}, osz[6] = {B * 4, B * 4, B * 8, B * 8, B * 24, slots * 4};
+  void* dev_in[4] = {(void*)in->n_seg, (void*)in->T, (void*)coef, (void*)in->t_from};
+  void* dev_out[6] = {user[0], user[1], user[2], user[3], user[4], user[5]};
+  if (host) {
+    size_t total = 0, ioff[4], ooff[6];
+    for (int i = 0; i < 4; i++) { ioff[i] = total; total += up(isz[i]); }
+    for (int i = 0; i < 6; i++) { ooff[i] = total; total += up(osz[i]); }
+    CHIP_TRY(plan_grow(h, &h->plan_io, &h->plan_io_bytes, total));
+    for (int i = 0; i < 4; i++) {
+      dev_in[i] = src[i] ? (char*)h->plan_io + ioff[i] : nullptr;
+      if (src[i]) CHIP_TRY(hipMemcpyAsync(dev_in[i], src[i], isz[i], hipMemcpyHostToDevice, h->stream));
+    }
+    for (int i = 0; i < 6; i++) dev_out[i] = user[i] ? (char*)h->plan_io + ooff[i] : nullptr;
+    if (dev_out[5]) CHIP_TRY(hipMemsetAsync(dev_out[5], 0xff, osz[5], h->stream));  // entries past n_seg read -1
+  }
+  A.n_seg = (const int32_t*)dev_in[0]; A.T = dev_in[1]; A.coef = dev_in[2]; A.t_from = (const double*)dev_in[3];
+  A.status = (int32_t*)dev_out[0]; A.verdict = (int32_t*)dev_out[1]; A.t_free = (double*)dev_out[2]; A.first = (int32_t*)dev_out[3];
+  A.hit_box = (int32_t*)dev_out[4]; A.seg_first = (int32_t*)dev_out[5];
+  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  hipError_t e = hipMemsetAsync(h->plan_ws, 0, 16, h->stream);
+  if (e == hipSuccess) e = in->dtype == DIRECT_F32 ? plan_check_launch<float>(D, A, h->stream) : plan_check_launch<double>(D, A, h->stream);
+  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
+  h->timed = e == hipSuccess;
+  if (host)
+    for (int i = 0; i < 6 && e == hipSuccess; i++)
+      if (user[i]) e = hipMemcpyAsync(user[i], dev_out[i], osz[i], hipMemcpyDeviceToHost, h->stream);
+  unsigned long long cnt[2] = {0, 0};
+  if (e == hipSuccess && out->stats) e = hipMemcpyAsync(cnt, h->plan_ws, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  hipError_t e2 = hipStreamSynchronize(h->stream);
+  if (e != hipSuccess || e2 != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, std::string("plan_check_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  if (out->stats) { out->stats[0] = (int64_t)(cnt[0] & 0xffffffffull); out->stats[1] = (int64_t)cnt[1]; }
   return DIRECT_OK;
 }
 

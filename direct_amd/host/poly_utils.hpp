@@ -72,6 +72,41 @@ class polyhedronGenerator {
     return stats[3];
   }
 
+  // One plan against the map the generator holds NOW (direct_cluster_plan_check_batch): polyCoeff(k, q) and time(k) as
+  // getPolyCoeff() / getPolyTime() give them (Eigen matrices or anything with the same call operators and time.size()).  Conservative:
+  // a blocked verdict means that a piece of the curve of duration T_i / 2^depth has a bounding box touching an occupied voxel, not
+  // that the curve enters it.  t_from < 0 judges the whole plan.
+  struct PlanCheck {
+    int verdict = DIRECT_PLAN_CHECK_INVALID;   // 0 clear; 1 occupied, 2 leaves the map, 3 both: the first blocked piece
+    double t_free = 0;                         // certified clear before this time on the plan's clock (t_total when clear)
+    int segment = -1, leaf = -1;               // the first blocked piece
+    int box[6] = {-1, -1, -1, -1, -1, -1};     // its voxel-index box, lo xyz, hi xyz
+    bool clear() const { return verdict == 0; }
+  };
+  template <class Mat, class Vec>
+  PlanCheck checkTrajectory(const Mat& polyCoeff, const Vec& time, int depth = 8, double margin = 0.0, double t_from = -1.0,
+                            bool outside_blocks = false) {
+    const int N = (int)time.size();
+    std::vector<double> poly((size_t)N * 18), T(N);
+    for (int k = 0; k < N; k++) {
+      T[k] = time(k);
+      for (int q = 0; q < 18; q++) poly[(size_t)k * 18 + q] = polyCoeff(k, q);
+    }
+    int32_t n_seg = N, status = 0, verdict = 0, first[2] = {-1, -1};
+    PlanCheck c;
+    direct_plan_check_in_t in{};
+    in.batch = 1; in.n_seg_max = N; in.mem = DIRECT_MEM_HOST; in.dtype = DIRECT_F64;
+    in.n_seg = &n_seg; in.T = T.data(); in.poly = poly.data();
+    for (int a = 0; a < 3; a++) in.map_lower[a] = lower_[a];
+    in.resolution = res_; in.margin = margin; in.depth = depth; in.outside_blocks = outside_blocks ? 1 : 0;
+    in.t_from = t_from < 0.0 ? nullptr : &t_from;
+    direct_plan_check_out_t out{};
+    out.status = &status; out.verdict = &verdict; out.t_free = &c.t_free; out.first = first; out.hit_box = c.box;
+    if (direct_cluster_plan_check_batch(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    c.verdict = verdict; c.segment = first[0]; c.leaf = first[1];
+    return c;
+  }
+
   std::array<int, 3> coord2Index(const std::array<double, 3>& c) const {  // :10-18
     auto f = [&](double v, double lo, int mx) {
       int i = (int)((v - lo) * inv_res_);

@@ -210,11 +210,95 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
                                                int32_t* path_xyz, int32_t* path_len, double* path_cost, double* dist,
                                                int32_t* stats, int32_t* rtn);
 
+/* ---- plans against the resident map: the step after a sensor update (no reference counterpart) --------------------
+ * Is each of these solved plans still clear of the map the handle holds NOW, and if not, until when is it safe?  The audit
+ * (direct_traj_audit_batch) judges a plan against the corridor it was solved in, which describes the map as it was; this call
+ * judges it against the voxels, with box tests on the handle's summed-area table alone: no root finding, no tolerance, every
+ * output a pure function of the inputs and bit for bit reproducible.
+ * batch, n_seg_max, mem, n_seg, T and exactly one of bez / poly: meaning, layouts and row validity as in direct_eval_in_t
+ * (include/direct_ddp.h, items 1 and 6 there); dtype (direct_dtype_t) is the storage type of T, bez and poly - the cluster
+ * handle has none of its own.  map_lower and resolution place the voxels, as in direct_cluster_map_from_cloud;
+ * inv = 1.0 / resolution is computed once on the host.  All arithmetic is double with contraction off, written with plain
+ * * and + (no fma), so that a NumPy restatement performs the same operations.  For a valid row of n segments:
+ *   1. Control points in metres, per segment and axis.  From bez: P_j = T * c_j.  From poly: P_j = sum_{m=0..j} w[j][m] *
+ *      (a_m * Tm), summed with ascending m, w[j][m] = (double)C(j,m) / (double)C(5,m), Tm by repeated multiplication
+ *      (T^0 = 1, T^m = T^(m-1) * T).
+ *   2. Leaves.  Leaf k (0 <= k < 2^D, D = depth) of a segment is the result of D de Casteljau halvings of its six points, every
+ *      new point (a + b) * 0.5; at step l the half is chosen by bit D-1-l of k (0: left, 1: right).  It spans the plan time
+ *      [S_i + (k * 2^-D) * T_i, S_i + ((k+1) * 2^-D) * T_i] - the factor exact, the product rounded, then the sum, S the
+ *      evaluation's cumulative sum; the end of a segment's last leaf is S_(i+1) to the bit.
+ *   3. Box of a leaf, per axis a: q_lo = ((min_j P_j[a] - margin) - map_lower[a]) * inv, q_hi = ((max_j P_j[a] + margin) -
+ *      map_lower[a]) * inv; the index is size[a] when q >= size[a], -1 when q < 0 (or q is NaN), else (int)q - compared before it
+ *      is converted: the voxel int((coord - lower) * inv) the map builder would have put the coordinate in.  The box LEAVES THE
+ *      MAP when any i_lo == -1 or any i_hi == size.  It is OCCUPIED when a voxel with byte 1 lies in its intersection with the
+ *      map (an empty intersection is not occupied).  It is BLOCKED when it is occupied, or when outside_blocks is set and it
+ *      leaves the map.
+ *   4. A leaf is judged iff its end time is > t_from[b] (t_from == NULL: every leaf).
+ *   5. Outputs (any but status may be NULL):
+ *      status [batch]           0 or -1 (required)
+ *      verdict [batch]          0: every judged leaf's box is unblocked - the continuous curve from t_from on lies in free voxels
+ *                               (inside the map too when outside_blocks is set); otherwise the facts about the first blocked
+ *                               judged leaf: 1 it is occupied, 2 it leaves the map, 3 both (bit 1 is reported whether or not
+ *                               outside_blocks is set); DIRECT_PLAN_CHECK_INVALID for an invalid row
+ *      t_free [batch] (double)  the start time of the first blocked judged leaf, in (segment, k) order; S_n when the verdict is
+ *                               0; 0 for an invalid row.  From t_from up to t_free the plan is certified clear: the time to hand
+ *                               to direct_traj_eval_batch for the start state of a replan.
+ *      first [batch][2]         that segment and leaf; (-1, -1) when there is none
+ *      hit_box [batch][6]       that leaf's i_lo[3], i_hi[3]; all -1 when there is none
+ *      seg_first [batch][n_seg_max]  the first blocked judged leaf of each segment, or -1.  Entries past n_seg are untouched in
+ *                               device memory and -1 in host memory; the first min(n_seg, n_seg_max) of an invalid row are -1.
+ *      stats (HOST, [2])        diagnostic: slots the first pass left to the deep pass, box tests made.  Asking for it adds
+ *                               one atomic add per wave.
+ *   6. A row is also invalid when t_from[b] is NaN, or when a control point of item 1 of its first n segments is NaN or larger
+ *      than 1e300 in magnitude (a non-finite coefficient always gives one; below that bound no halving can overflow).
+ *      Invalid rows: status = -1, verdict = DIRECT_PLAN_CHECK_INVALID, t_free = 0, -1 in first, hit_box and seg_first; other
+ *      rows are unaffected.
+ * CONSERVATIVE BY CONSTRUCTION: a curve lies in the convex hull of its control points, so an unblocked leaf proves its piece of
+ * the curve clear.  A blocked verdict means that a piece of the curve of duration T_i / 2^D has a bounding box that touches an
+ * occupied voxel (or leaves the map); it does NOT mean that the curve enters that voxel.  A larger depth shrinks the boxes.
+ * The result is that of judging all 2^D leaves of every segment one by one; the kernels find it by descending the halving tree
+ * and skipping every subtree whose own box is unblocked or that ends at or before t_from (DESIGN.md 6.12 has the argument).
+ * DIRECT_ERR_INVALID, nothing launched: a NULL handle / struct / n_seg / T / status; a non-positive batch / n_seg_max; not
+ * exactly one of bez and poly; an unknown mem or dtype; depth outside [0, 12]; a non-finite map_lower; margin < 0 or not
+ * finite; resolution <= 0 or not finite; outside_blocks not 0 or 1; a handle without a map.  DIRECT_ERR_UNSUPPORTED: batch *
+ * n_seg_max of 2^31 or more.  Runs on the handle's stream and synchronises before it returns; direct_cluster_last_ms covers its
+ * kernels (not the copies of host arrays).  Its workspace (8 B per row and 16 B per segment slot) and the staging of host
+ * arrays grow on demand and are freed in direct_cluster_destroy.  It leaves resident clusters and the path workspace alone. */
+#define DIRECT_PLAN_CHECK_INVALID (-1)
+typedef struct {
+  int32_t batch, n_seg_max;
+  int32_t mem;               /* direct_mem_t: where every array of `in` and `out` lives (out->stats: always host) */
+  int32_t dtype;             /* direct_dtype_t: storage type of T, bez, poly */
+  const int32_t* n_seg;      /* [batch] */
+  const void* T;             /* [batch][n_seg_max] */
+  const void* bez;           /* [batch][n_seg_max][18] or NULL } exactly one */
+  const void* poly;          /* [batch][n_seg_max][18] or NULL }            */
+  double map_lower[3];
+  double resolution;
+  double margin;             /* >= 0 metres added to every box on each side; 0: the map is already inflated */
+  int32_t depth;             /* D in [0, 12] */
+  int32_t outside_blocks;    /* 0 / 1 */
+  const double* t_from;      /* [batch] or NULL */
+} direct_plan_check_in_t;
+
+typedef struct {
+  int32_t* status;           /* [batch], required */
+  int32_t* verdict;          /* [batch] or NULL */
+  double* t_free;            /* [batch] or NULL */
+  int32_t* first;            /* [batch][2] or NULL */
+  int32_t* hit_box;          /* [batch][6] or NULL */
+  int32_t* seg_first;        /* [batch][n_seg_max] or NULL */
+  int64_t* stats;            /* HOST [2] or NULL */
+} direct_plan_check_out_t;
+
+direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in,
+                                                direct_plan_check_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
- * grid_path_batch / map_from_cloud call */
+ * grid_path_batch / map_from_cloud / plan_check_batch call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
