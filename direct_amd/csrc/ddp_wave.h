@@ -894,6 +894,17 @@ struct Wave {
   // the gains of phase D) in ONE batch of loads; with double storage the same batches spill inside the sweeps, and a
   // spill reload waits for every outstanding load, the HBM prefetch included
   static constexpr bool kWide = sizeof(St) < sizeof(double) && RPL <= 2;
+  // Joint phase T of a pair round (run_round): terms per batch of operand loads (3 + 2 * 2 doubles a term; 1, 2, 3 or 6) and
+  // whether batch b + 1 is loaded before batch b is summed.  One term a batch, pipelined, is the form that keeps the rounds of
+  // every 168-VGPR instantiation free of scratch.  -DDDP_JOINT_TERMS / -DDDP_JOINT_PIPE: A/B builds.
+#ifndef DDP_JOINT_TERMS
+#define DDP_JOINT_TERMS 1
+#endif
+#ifndef DDP_JOINT_PIPE
+#define DDP_JOINT_PIPE 1
+#endif
+  static constexpr int kJointTerms = DDP_JOINT_TERMS;
+  static constexpr bool kJointPipe = DDP_JOINT_PIPE != 0;
   // Field widths of the packed row descriptor: rows fit eight bits up to four row slots per lane (6 P + 55 <= 255);
   // the kernels with five to eight slots (polytopes of 34 .. 76 planes: 6 P + 55 <= 511) take a ninth bit from a0 (< 64),
   // those with ten to fourteen (up to 128 planes: 6 P + 55 <= 823) a tenth.
@@ -3025,129 +3036,292 @@ struct Wave {
       for (int j = 0; j < 6; j++) pwo[j] = (j == 0) ? (Real)1 : DDP_UNIFORM_R(pow3(To, To2, To4, j));
       Real Tn[NT];
       Real pwn[NT][6];
+      // Both trials of a pair alive (wave-uniform): phases D and T evaluate them TOGETHER - the gains, the old controls
+      // and the old control values are loaded / formed once, and the two dependent chains share every load wait.  Each
+      // trial's own operations, and their order, are those of the per-trial bodies below.
+      const bool joint = NT == 2 && tr[0].alive && tr[NT - 1].alive;
+      if (joint) {
+        PLA(Real, unew, NT);
+        PLA(Real, dxl, NT);
+        PLA(Real, kr, 9);
+        PLV(Real, zlv);
+        PLV(Real, kfv);
+        LANES {
+          const int lx = lane & 15;
+          const int l9 = lx < 9 ? lx : 8;
+          Real xv[NT];
 #pragma unroll
-      for (int t = 0; t < NT; t++) {
-        Tn[t] = (Real)0;
-        if (tr[t].alive) {
-          typename Lds::FwdT& F = L.ft[t];
-          PLV(Real, unew);
-          PLV(Real, dxl);
-          // x lanes: 0..8, and a second copy in lanes 16..24 of the ROW OF 16 that holds the ten u lanes (16..25): every
-          // dx[c] then reaches the u lanes as a DPP row broadcast folded into the FMA, not through two v_readlane
-          PLA(Real, kr, 9);
-          PLV(Real, zlv);
-          PLV(Real, kfv);
-          LANES {
-            const int lx = lane & 15;
-            const int l9 = lx < 9 ? lx : 8;
-            const Real xv = F.xn[l9];
-            const Real zv = L.z[l9];
-            // the u lanes' gains and old controls in the same batch of loads (lanes outside 16..25 read lane 25's)
-            const int a = lane < 16 ? 0 : (lane < 26 ? lane - 16 : 9);
-            if (kWide) {
+          for (int t = 0; t < NT; t++) xv[t] = L.ft[t].xn[l9];
+          const Real zv = L.z[l9];
+          const int a = lane < 16 ? 0 : (lane < 26 ? lane - 16 : 9);
+          if (kWide) {
+#pragma unroll
+            for (int c = 0; c < 9; c++) LV(kr)[c] = L.KUr[10 + a * 9 + c];
+            LV(zlv) = L.z[9 + a];
+            LV(kfv) = L.KUr[a];
+          }
+          DDP_LOADS_ISSUED();
+#pragma unroll
+          for (int t = 0; t < NT; t++) {
+            LV(dxl)[t] = xv[t] - zv;
+            if (lane < 9) {
+              L.ft[t].dz[lane] = LV(dxl)[t];
+              L.ft[t].zn[lane] = xv[t];
+            }
+          }
+#pragma unroll
+          for (int t = 0; t < NT; t++) ROW_HAZARD(LV(dxl)[t]);
+        }
+        LANES {
+#pragma unroll
+          for (int t = 0; t < NT; t++) LV(unew)[t] = (Real)0;
+          if (lane >= 16 && lane < 26) {
+            const int a = lane - 16;
+            if (!kWide) {
 #pragma unroll
               for (int c = 0; c < 9; c++) LV(kr)[c] = L.KUr[10 + a * 9 + c];
               LV(zlv) = L.z[9 + a];
               LV(kfv) = L.KUr[a];
+              DDP_LOADS_ISSUED();
             }
-            DDP_LOADS_ISSUED();
-            LV(dxl) = xv - zv;
-            if (lane < 9) {
-              F.dz[lane] = LV(dxl);
-              F.zn[lane] = xv;
-            }
-            ROW_HAZARD(LV(dxl));
-          }
-          LANES {
-            LV(unew) = (Real)0;
-            if (lane >= 16 && lane < 26) {
-              const int a = lane - 16;
-              if (!kWide) {  // double storage: no registers to carry them across the block boundary
+            Real acc[NT];
 #pragma unroll
-                for (int c = 0; c < 9; c++) LV(kr)[c] = L.KUr[10 + a * 9 + c];
-                LV(zlv) = L.z[9 + a];
-                LV(kfv) = L.KUr[a];
-                DDP_LOADS_ISSUED();
-              }
-              Real acc = 0;
-              static_for<0, 9>([&](auto C) {
-                constexpr int c = C;
-                ROW_FMA_V(acc, dxl, c, LV(kr)[c]);
-              });
-              // du = alpha ku + Ku dx: the whole step of the controls.  The rows of phase R multiply [dx; du], which
-              // is how the slack / dual gains are eliminated (see there)
-              const Real du = fma(alpha[t], LV(kfv), acc);
-              F.dz[9 + a] = du;
-              // every new quantity is rounded to the storage type BEFORE it is used, so that the recorded
-              // cost / log-barrier belong exactly to the iterate that is stored (DESIGN.md "Precision")
+            for (int t = 0; t < NT; t++) acc[t] = 0;
+            static_for<0, 9>([&](auto C) {
+              constexpr int c = C;
+#pragma unroll
+              for (int t = 0; t < NT; t++) ROW_FMA(acc[t], dxl, t, c, LV(kr)[c]);
+            });
+#pragma unroll
+            for (int t = 0; t < NT; t++) {
+              const Real du = fma(alpha[t], LV(kfv), acc[t]);
+              L.ft[t].dz[9 + a] = du;
               const Real un = pair_round(LV(zlv) + du);
-              F.zn[9 + a] = un;
-              LV(unew) = un;
+              L.ft[t].zn[9 + a] = un;
+              LV(unew)[t] = un;
             }
           }
-          Tn[t] = RDLANE_V(unew, 25);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          Tn[t] = RDLANE(unew, t, 25);
           const Real Tn2 = DDP_UNIFORM_PW(Tn[t] * Tn[t]), Tn4 = DDP_UNIFORM_PW(Tn2 * Tn2);
 #pragma unroll
           for (int j = 0; j < 6; j++) pwn[t][j] = (j == 0) ? (Real)1 : DDP_UNIFORM_PW(pow3(Tn[t], Tn2, Tn4, j));
           if (Tn[t] < 0) tr[t].neg = 1;
         }
+      } else {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          Tn[t] = (Real)0;
+          if (tr[t].alive) {
+            typename Lds::FwdT& F = L.ft[t];
+            PLV(Real, unew);
+            PLV(Real, dxl);
+            // x lanes: 0..8, and a second copy in lanes 16..24 of the ROW OF 16 that holds the ten u lanes (16..25): every
+            // dx[c] then reaches the u lanes as a DPP row broadcast folded into the FMA, not through two v_readlane
+            PLA(Real, kr, 9);
+            PLV(Real, zlv);
+            PLV(Real, kfv);
+            LANES {
+              const int lx = lane & 15;
+              const int l9 = lx < 9 ? lx : 8;
+              const Real xv = F.xn[l9];
+              const Real zv = L.z[l9];
+              // the u lanes' gains and old controls in the same batch of loads (lanes outside 16..25 read lane 25's)
+              const int a = lane < 16 ? 0 : (lane < 26 ? lane - 16 : 9);
+              if (kWide) {
+#pragma unroll
+                for (int c = 0; c < 9; c++) LV(kr)[c] = L.KUr[10 + a * 9 + c];
+                LV(zlv) = L.z[9 + a];
+                LV(kfv) = L.KUr[a];
+              }
+              DDP_LOADS_ISSUED();
+              LV(dxl) = xv - zv;
+              if (lane < 9) {
+                F.dz[lane] = LV(dxl);
+                F.zn[lane] = xv;
+              }
+              ROW_HAZARD(LV(dxl));
+            }
+            LANES {
+              LV(unew) = (Real)0;
+              if (lane >= 16 && lane < 26) {
+                const int a = lane - 16;
+                if (!kWide) {  // double storage: no registers to carry them across the block boundary
+#pragma unroll
+                  for (int c = 0; c < 9; c++) LV(kr)[c] = L.KUr[10 + a * 9 + c];
+                  LV(zlv) = L.z[9 + a];
+                  LV(kfv) = L.KUr[a];
+                  DDP_LOADS_ISSUED();
+                }
+                Real acc = 0;
+                static_for<0, 9>([&](auto C) {
+                  constexpr int c = C;
+                  ROW_FMA_V(acc, dxl, c, LV(kr)[c]);
+                });
+                // du = alpha ku + Ku dx: the whole step of the controls.  The rows of phase R multiply [dx; du], which
+                // is how the slack / dual gains are eliminated (see there)
+                const Real du = fma(alpha[t], LV(kfv), acc);
+                F.dz[9 + a] = du;
+                // every new quantity is rounded to the storage type BEFORE it is used, so that the recorded
+                // cost / log-barrier belong exactly to the iterate that is stored (DESIGN.md "Precision")
+                const Real un = pair_round(LV(zlv) + du);
+                F.zn[9 + a] = un;
+                LV(unew) = un;
+              }
+            }
+            Tn[t] = RDLANE_V(unew, 25);
+            const Real Tn2 = DDP_UNIFORM_PW(Tn[t] * Tn[t]), Tn4 = DDP_UNIFORM_PW(Tn2 * Tn2);
+#pragma unroll
+            for (int j = 0; j < 6; j++) pwn[t][j] = (j == 0) ? (Real)1 : DDP_UNIFORM_PW(pow3(Tn[t], Tn2, Tn4, j));
+            if (Tn[t] < 0) tr[t].neg = 1;
+          }
+        }
       }
       WSYNC();
     DDP_MARK("F_T");
       // ---- T: control values at the old and at the new iterate, A * [dx; du], x+, jerk cost
+      if (joint) {
+        LANES {
+          {  // (lane roles, lt[7] and the order of the terms: see the per-trial body below)
+            const int l62 = lane < 63 ? lane : 62;
+            const int w2 = kWide ? LV(tw_ft) : L.lt[7][lane];
+            const int wbb = w2 & 1023, o = (w2 >> 17) & 3;
+            const Real* zop = byte_at(L.z, (w2 >> 10) & 127);
+            const Real *dzp[NT], *znp[NT];
+            Real vn[NT], gf[NT];
 #pragma unroll
-      for (int t = 0; t < NT; t++) {
-        if (tr[t].alive) {
-          typename Lds::FwdT& F = L.ft[t];
-          LANES {
-            {  // lanes 0..44: control values; 45..53: x+ (rows of [F|G]); 54..62: jerk-cost products (rows of R)
-              const int l62 = lane < 63 ? lane : 62;
-              // lt[7] (loaded in phase L): byte offsets of the row's first live weight WbE[cr][o] and of entry 3 o + d of
-              // a knot record, and o - see phase T2 of the backward sweep; terms past the end of the row read a zero
-              // weight against entries 19..23 of the records, which the round's prologue has zeroed
-              const int w2 = kWide ? LV(tw_ft) : L.lt[7][lane];  // (double storage: no register to carry it from phase L)
-              const int wbb = w2 & 1023, o = (w2 >> 17) & 3;
-              const Real* zop = byte_at(L.z, (w2 >> 10) & 127);
-              const Real* dzp = byte_at(F.dz, (w2 >> 10) & 127);
-              const Real* znp = byte_at(F.zn, (w2 >> 10) & 127);
-              Real dvo = 0, vn = 0, gf = 0, vo = 0;
-              // Summed over the exponent j = i - o instead of the coefficient index i (same terms, same
-              // order: the i < o terms have zero weight): the power T^j is then the same for every lane and
-              // comes from a uniform register instead of three LDS table reads per term.
+            for (int t = 0; t < NT; t++) {
+              dzp[t] = byte_at(L.ft[t].dz, (w2 >> 10) & 127);
+              znp[t] = byte_at(L.ft[t].zn, (w2 >> 10) & 127);
+              vn[t] = 0;
+              gf[t] = 0;
+            }
+            Real dvo = 0, vo = 0;  // the old iterate's: formed once for both trials
+            // Operand batches of kJointTerms terms, 3 + 2 NT doubles a term, software-pipelined: batch b + 1 is in flight
+            // while batch b is summed.  The accumulators are pinned batch by batch - left alone, the compiler sinks all six
+            // terms' arithmetic below the last load (into the masked stores), and every operand is live at once.
+            Real wb6[6], wd6[6], zo6[6], dz6[NT][6], zn6[NT][6];
+            auto load_terms = [&](int j0) {
 #pragma unroll
-              for (int half = 0; half < 2; half++) {  // two batches of 15 operands
-                Real wb6[3], wd6[3], zo6[3], dz6[3], zn6[3];
+              for (int j = j0; j < j0 + kJointTerms; j++) {
+                const int wa = (j < 4 || j + o < 6) ? wbb + j * (int)sizeof(Real) : 108 * (int)sizeof(Real);
+                wb6[j] = *byte_at(L.WbE, wa);
+                wd6[j] = *byte_at(L.WdE, wa);
+                zo6[j] = zop[3 * j];
 #pragma unroll
-                for (int jj = 0; jj < 3; jj++) {
-                  const int j = 3 * half + jj;
-                  const int wa = (j < 4 || j + o < 6) ? wbb + j * (int)sizeof(Real) : 108 * (int)sizeof(Real);
-                  wb6[jj] = *byte_at(L.WbE, wa);
-                  wd6[jj] = *byte_at(L.WdE, wa);
-                  zo6[jj] = zop[3 * j];
-                  dz6[jj] = dzp[3 * j];
-                  zn6[jj] = znp[3 * j];
-                }
-                DDP_LOADS_ISSUED();
-#pragma unroll
-                for (int jj = 0; jj < 3; jj++) {
-                  const int j = 3 * half + jj;
-                  const Real w = wb6[jj] * pwo[j];
-                  vo += w * zo6[jj];  // the old control values (every alive trial writes the same ones)
-                  gf += w * dz6[jj];
-                  dvo += wd6[jj] * pwo[j < 1 ? 0 : j - 1] * zo6[jj];
-                  vn += wb6[jj] * pwn[t][j] * zn6[jj];
+                for (int t = 0; t < NT; t++) {
+                  dz6[t][j] = dzp[t][3 * j];
+                  zn6[t][j] = znp[t][3 * j];
                 }
               }
-              const Real un = F.zn[9 + (lane < 54 ? 0 : l62 - 54)], dT = F.dz[18];
-              if (lane < 45) F.G[lane] = gf + dvo * dT;
-              if (lane < 45) L.val[lane] = vo;
-              Real* dst = lane < 45 ? &F.valn[l62] : (lane < 54 ? &F.xnx[l62 - 45] : &F.qp[l62 - 54]);
-              *dst = lane < 54 ? vn : vn * un;  // u_a[d] * (R u)_a[d]: the nine of them sum to u'Ru (DDP:1294-1305)
+            };
+            if (kJointPipe) load_terms(0);
+#pragma unroll
+            for (int j0 = 0; j0 < 6; j0 += kJointTerms) {
+              if (!kJointPipe) load_terms(j0);
+              else if (j0 + kJointTerms < 6) load_terms(j0 + kJointTerms);
+              DDP_LOADS_ISSUED();
+#pragma unroll
+              for (int j = j0; j < j0 + kJointTerms; j++) {
+                const Real w = wb6[j] * pwo[j];
+                vo += w * zo6[j];
+#pragma unroll
+                for (int t = 0; t < NT; t++) gf[t] += w * dz6[t][j];
+                dvo += wd6[j] * pwo[j < 1 ? 0 : j - 1] * zo6[j];
+#pragma unroll
+                for (int t = 0; t < NT; t++) vn[t] += wb6[j] * pwn[t][j] * zn6[t][j];
+              }
+              DDP_PIN(vo);
+              DDP_PIN(dvo);
+#pragma unroll
+              for (int t = 0; t < NT; t++) {
+                DDP_PIN(gf[t]);
+                DDP_PIN(vn[t]);
+              }
+              DDP_LOADS_ISSUED();  // (the next batch's loads stay below the pins)
             }
-            if (lane == 63) {
-              F.valn[45] = F.zn[18];
-              F.G[45] = F.dz[18];
-              L.val[45] = L.z[18];
+            if (lane < 45) L.val[lane] = vo;
+#pragma unroll
+            for (int t = 0; t < NT; t++) {
+              typename Lds::FwdT& F = L.ft[t];
+              const Real un = F.zn[9 + (lane < 54 ? 0 : l62 - 54)], dT = F.dz[18];
+              if (lane < 45) F.G[lane] = gf[t] + dvo * dT;
+              Real* dst = lane < 45 ? &F.valn[l62] : (lane < 54 ? &F.xnx[l62 - 45] : &F.qp[l62 - 54]);
+              *dst = lane < 54 ? vn[t] : vn[t] * un;
+            }
+          }
+          if (lane == 63) {
+#pragma unroll
+            for (int t = 0; t < NT; t++) {
+              L.ft[t].valn[45] = L.ft[t].zn[18];
+              L.ft[t].G[45] = L.ft[t].dz[18];
+            }
+            L.val[45] = L.z[18];
+          }
+        }
+      } else {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+          if (tr[t].alive) {
+            typename Lds::FwdT& F = L.ft[t];
+            LANES {
+              {  // lanes 0..44: control values; 45..53: x+ (rows of [F|G]); 54..62: jerk-cost products (rows of R)
+                const int l62 = lane < 63 ? lane : 62;
+                // lt[7] (loaded in phase L): byte offsets of the row's first live weight WbE[cr][o] and of entry 3 o + d of
+                // a knot record, and o - see phase T2 of the backward sweep; terms past the end of the row read a zero
+                // weight against entries 19..23 of the records, which the round's prologue has zeroed
+                const int w2 = kWide ? LV(tw_ft) : L.lt[7][lane];  // (double storage: no register to carry it from phase L)
+                const int wbb = w2 & 1023, o = (w2 >> 17) & 3;
+                const Real* zop = byte_at(L.z, (w2 >> 10) & 127);
+                const Real* dzp = byte_at(F.dz, (w2 >> 10) & 127);
+                const Real* znp = byte_at(F.zn, (w2 >> 10) & 127);
+                Real dvo = 0, vn = 0, gf = 0, vo = 0;
+                // Summed over the exponent j = i - o instead of the coefficient index i (same terms, same
+                // order: the i < o terms have zero weight): the power T^j is then the same for every lane and
+                // comes from a uniform register instead of three LDS table reads per term.
+#pragma unroll
+                for (int half = 0; half < 2; half++) {  // two batches of 15 operands
+                  Real wb6[3], wd6[3], zo6[3], dz6[3], zn6[3];
+#pragma unroll
+                  for (int jj = 0; jj < 3; jj++) {
+                    const int j = 3 * half + jj;
+                    const int wa = (j < 4 || j + o < 6) ? wbb + j * (int)sizeof(Real) : 108 * (int)sizeof(Real);
+                    wb6[jj] = *byte_at(L.WbE, wa);
+                    wd6[jj] = *byte_at(L.WdE, wa);
+                    zo6[jj] = zop[3 * j];
+                    dz6[jj] = dzp[3 * j];
+                    zn6[jj] = znp[3 * j];
+                  }
+                  DDP_LOADS_ISSUED();
+#pragma unroll
+                  for (int jj = 0; jj < 3; jj++) {
+                    const int j = 3 * half + jj;
+                    const Real w = wb6[jj] * pwo[j];
+                    vo += w * zo6[jj];  // the old control values (every alive trial writes the same ones)
+                    gf += w * dz6[jj];
+                    dvo += wd6[jj] * pwo[j < 1 ? 0 : j - 1] * zo6[jj];
+                    vn += wb6[jj] * pwn[t][j] * zn6[jj];
+                  }
+                  if (NT == 2) {  // (scheduling only: see the joint body above; the single round's code is untouched)
+                    DDP_PIN(vo);
+                    DDP_PIN(gf);
+                    DDP_PIN(dvo);
+                    DDP_PIN(vn);
+                  }
+                }
+                const Real un = F.zn[9 + (lane < 54 ? 0 : l62 - 54)], dT = F.dz[18];
+                if (lane < 45) F.G[lane] = gf + dvo * dT;
+                if (lane < 45) L.val[lane] = vo;
+                Real* dst = lane < 45 ? &F.valn[l62] : (lane < 54 ? &F.xnx[l62 - 45] : &F.qp[l62 - 54]);
+                *dst = lane < 54 ? vn : vn * un;  // u_a[d] * (R u)_a[d]: the nine of them sum to u'Ru (DDP:1294-1305)
+              }
+              if (lane == 63) {
+                F.valn[45] = F.zn[18];
+                F.G[45] = F.dz[18];
+                L.val[45] = L.z[18];
+              }
             }
           }
         }
