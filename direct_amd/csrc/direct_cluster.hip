@@ -26,11 +26,11 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/direct_cluster.h"
 #include "grid_path_math.h"
+#include "host_stage.h"
 #include "hull_core.h"
 
 namespace {
@@ -1005,26 +1005,20 @@ struct direct_cluster_handle_s {
   int32_t *st_vertex = nullptr, *st_xyz = nullptr, *st_num = nullptr, *st_iters = nullptr, *st_rtn = nullptr;  // device staging of host outputs
   bool have_map = false;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
+  hs::EventPair ev;  // direct_cluster_last_ms
   std::vector<void*> allocs;
   HullDev H = {};          // scratch of hull_planes_batch, allocated by its first call
   bool have_hull = false;
   int convex_grid = 2048;    // workgroups per seed of k_convex (DIRECT_CLUSTER_CONVEX_GRID: experiments)
   int resident_batch = 0;    // seeds of the last polygon_generation_batch whose clusters are still in D.cluster / D.el (0: none)
-  void* hull_out = nullptr;  // device staging of its host outputs
-  size_t hull_out_bytes = 0;
+  hs::Block hull_out;        // device staging of its host outputs
   PathDev P = {};            // workspace of grid_path_batch, allocated by its first call (never shrunk, freed in destroy)
   bool have_path = false;
-  void* path_out = nullptr;  // the read-back ring and the device staging of its host outputs, grown with path_capacity
-  size_t path_out_bytes = 0;
-  float* cloud_in = nullptr;  // device staging of a host cloud of map_from_cloud, grown on demand
-  size_t cloud_in_bytes = 0;
+  hs::Block path_out;        // the read-back ring and the device staging of its host outputs, grown with path_capacity
+  hs::Block cloud_in;        // device staging of a host cloud of map_from_cloud, grown on demand
   unsigned long long* cloud_cnt = nullptr;  // [2] its counters
-  void* plan_ws = nullptr;    // workspace of plan_check_batch (counters, start times, per-slot leaves, unresolved list), grown on demand
-  size_t plan_ws_bytes = 0;
-  void* plan_io = nullptr;    // device staging of its host arrays, grown on demand
-  size_t plan_io_bytes = 0;
+  hs::Block plan_ws;  // workspace of plan_check_batch (counters, start times, per-slot leaves, unresolved list), grown on demand
+  hs::Block plan_io;  // device staging of its host arrays, grown on demand
 };
 
 namespace {
@@ -1070,38 +1064,30 @@ direct_status_t direct_cluster_create(const direct_cluster_config_t* cfg, direct
   D.G = cfg->max_x * cfg->max_y * cfg->max_z;
   D.ccap = cfg->cluster_capacity; D.kcap = cfg->candidate_capacity; D.kwords = (cfg->candidate_capacity + 63) / 64;
   const size_t B = cfg->max_batch, G = D.G;
-  direct_status_t st = DIRECT_OK;
-  auto A = [&](auto pp, size_t bytes) {
-    if (st != DIRECT_OK) return;
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-    if (e != hipSuccess) { st = cfail(DIRECT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); return; }
-    h->allocs.push_back(q);
-    *pp = (typename std::remove_pointer<decltype(pp)>::type)q;
-  };
   D.sat_z = cfg->max_z + 1; D.sat_yz = (cfg->max_y + 1) * D.sat_z;
-  A(&D.sat, (size_t)(cfg->max_x + 1) * D.sat_yz * sizeof(int));
   D.nchunk = (cfg->cluster_capacity + 255) / 256;
   float* invp = nullptr;
-  A(&invp, kDimLimit * sizeof(float));
+  const hipError_t ae = hs::alloc_all(h->allocs, {
+      hs::want(&D.sat, (size_t)(cfg->max_x + 1) * D.sat_yz * sizeof(int)), hs::want(&invp, kDimLimit * sizeof(float)),
+      hs::want(&D.cbox, B * (size_t)D.nchunk * 6 * sizeof(int)),
+      hs::want(&h->map, G), hs::want(&h->inside_tmp, G), hs::want(&h->seeds, B * 3 * sizeof(int)),
+      hs::want(&D.flags, B * G), hs::want(&D.key, B * G * sizeof(int)),
+      hs::want(&D.cluster, B * D.ccap * sizeof(int)), hs::want(&D.active, B * D.ccap * sizeof(int)), hs::want(&D.cand, B * D.kcap * sizeof(int)),
+      hs::want(&D.can_clu, B * D.kcap), hs::want(&D.accept, B * D.kcap),
+      hs::want(&D.blocked, B * D.kcap * (size_t)D.kwords * sizeof(unsigned long long)),
+      hs::want(&D.accbits, B * (size_t)D.kwords * sizeof(unsigned long long)), hs::want(&D.accpre, B * (size_t)D.kwords * sizeof(int)),
+      hs::want(&D.el, B * sizeof(Elem)),
+      hs::want(&D.ccnt, B * kCompactBlocks * sizeof(int)), hs::want(&D.csnap, B * 2 * sizeof(int)),
+      hs::want(&h->st_vertex, B * 24 * 4), hs::want(&h->st_xyz, B * (size_t)D.ccap * 12), hs::want(&h->st_num, B * 4),
+      hs::want(&h->st_iters, B * 4), hs::want(&h->st_rtn, B * 4)});
+  direct_status_t st = ae == hipSuccess ? DIRECT_OK : cfail(DIRECT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(ae));
   D.inv = invp;
-  A(&D.cbox, B * (size_t)D.nchunk * 6 * sizeof(int));
-  A(&h->map, G); A(&h->inside_tmp, G); A(&h->seeds, B * 3 * sizeof(int));
-  A(&D.flags, B * G); A(&D.key, B * G * sizeof(int));
-  A(&D.cluster, B * D.ccap * sizeof(int)); A(&D.active, B * D.ccap * sizeof(int)); A(&D.cand, B * D.kcap * sizeof(int));
-  A(&D.can_clu, B * D.kcap); A(&D.accept, B * D.kcap);
-  A(&D.blocked, B * D.kcap * (size_t)D.kwords * sizeof(unsigned long long));
-  A(&D.accbits, B * (size_t)D.kwords * sizeof(unsigned long long)); A(&D.accpre, B * (size_t)D.kwords * sizeof(int));
-  A(&D.el, B * sizeof(Elem));
-  A(&D.ccnt, B * kCompactBlocks * sizeof(int)); A(&D.csnap, B * 2 * sizeof(int));
-  A(&h->st_vertex, B * 24 * 4); A(&h->st_xyz, B * (size_t)D.ccap * 12); A(&h->st_num, B * 4); A(&h->st_iters, B * 4); A(&h->st_rtn, B * 4);
   D.map = h->map;
   if (st == DIRECT_OK) {
     hipLaunchKernelGGL(k_inv_table, dim3(1), dim3(256), 0, nullptr, invp);
     if (hipDeviceSynchronize() != hipSuccess) st = cfail(DIRECT_ERR_DEVICE, "k_inv_table failed");
   }
-  if (st == DIRECT_OK && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess))
-    st = cfail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
+  if (st == DIRECT_OK && hs::create(h->ev) != hipSuccess) st = cfail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
   if (st != DIRECT_OK) {
     direct_cluster_destroy(h);
     return st;
@@ -1115,13 +1101,8 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipSetDevice(h->cfg.device);
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
-  if (h->hull_out) (void)hipFree(h->hull_out);
-  if (h->path_out) (void)hipFree(h->path_out);
-  if (h->cloud_in) (void)hipFree(h->cloud_in);
-  if (h->plan_ws) (void)hipFree(h->plan_ws);
-  if (h->plan_io) (void)hipFree(h->plan_io);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io}) hs::release(*b);
+  hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
 }
@@ -1161,30 +1142,17 @@ direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const d
   C.size[0] = D.max_x; C.size[1] = D.max_y; C.size[2] = D.max_z;
   mc::inf_steps(p->cloud_margin, p->resolution, &C.s, &C.sz);
   C.border = p->border; C.stride = p->stride; C.n = n_points; C.map = h->map;
-  if (!h->cloud_cnt) {
-    void* q = nullptr;
-    CHIP_TRY(hipMalloc(&q, 2 * sizeof(unsigned long long)));
-    h->allocs.push_back(q);
-    h->cloud_cnt = (unsigned long long*)q;
-  }
+  if (!h->cloud_cnt) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->cloud_cnt, 2 * sizeof(unsigned long long))}));
   C.cnt = h->cloud_cnt;
   const size_t bytes = (size_t)n_points * p->stride * sizeof(float);
   if (mem == DIRECT_MEM_HOST && n_points > 0) {
-    if (bytes > h->cloud_in_bytes) {
-      if (h->cloud_in) {
-        CHIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->cloud_in);
-        h->cloud_in = nullptr; h->cloud_in_bytes = 0;
-      }
-      CHIP_TRY(hipMalloc((void**)&h->cloud_in, bytes));
-      h->cloud_in_bytes = bytes;
-    }
-    CHIP_TRY(hipMemcpyAsync(h->cloud_in, xyz, bytes, hipMemcpyHostToDevice, h->stream));
-    C.xyz = h->cloud_in;
+    CHIP_TRY(hs::grow(h->cloud_in, h->stream, bytes));
+    CHIP_TRY(hipMemcpyAsync(h->cloud_in.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+    C.xyz = (const float*)h->cloud_in.p;
   } else {
     C.xyz = xyz;
   }
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
   hipError_t e = hipMemsetAsync(h->cloud_cnt, 0, 2 * sizeof(unsigned long long), h->stream);
   if (e == hipSuccess && (p->mode == DIRECT_MAP_REPLACE || !h->have_map)) e = hipMemsetAsync(h->map, 0, (size_t)D.G, h->stream);
   if (e == hipSuccess && n_points > 0) {
@@ -1194,18 +1162,17 @@ direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const d
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = rebuild_sat(h);
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  h->timed = e == hipSuccess;
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   unsigned long long cnt[2] = {0, 0};
   int occupied = 0;  // the table's last entry is the sum over the whole map: the count and the table cannot disagree
   if (e == hipSuccess && stats) e = hipMemcpyAsync(cnt, h->cloud_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && stats)
     e = hipMemcpyAsync(&occupied, D.sat + ((size_t)(D.max_x + 1) * D.sat_yz - 1), sizeof(int), hipMemcpyDeviceToHost, h->stream);
-  hipError_t e2 = hipStreamSynchronize(h->stream);
+  e = hs::drain(h->stream, e);
   // the map has been touched: whatever happened, an earlier table no longer describes it
-  if (e != hipSuccess || e2 != hipSuccess) {
+  if (e != hipSuccess) {
     h->have_map = false;
-    return cfail(DIRECT_ERR_DEVICE, std::string("map_from_cloud: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+    return cfail(DIRECT_ERR_DEVICE, std::string("map_from_cloud: ") + hipGetErrorString(e));
   }
   h->have_map = true;
   if (stats) { stats[0] = n_points; stats[1] = (int64_t)cnt[0]; stats[2] = (int64_t)cnt[1]; stats[3] = occupied; }
@@ -1235,7 +1202,7 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
   Dev& D = h->D;
   h->resident_batch = 0;
   CHIP_TRY(hipMemcpyAsync(h->seeds, seeds, (size_t)batch * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
   const int gblocks = std::min((D.G + 255) / 256, 4096);
   hipLaunchKernelGGL(k_flags_init, dim3(gblocks, batch), dim3(256), 0, h->stream, D, (const uint8_t*)nullptr);  // flagClear CS:20-26
   hipLaunchKernelGGL(k_inflate, dim3(batch), dim3(256), 0, h->stream, D, (const int*)h->seeds, itr_inflate_max);
@@ -1278,15 +1245,13 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
     CHIP_TRY(fetch());
   }
   int32_t *dv = vertex_idx, *dc = cluster_xyz, *dn = cluster_num, *di = cluster_iters, *dr = rtn;
-  auto cleanup = [&]() {};
   if (mem == DIRECT_MEM_HOST) {  // host outputs are staged in buffers the handle owns (allocated once, in create)
     dv = vertex_idx ? h->st_vertex : nullptr; dc = cluster_xyz ? h->st_xyz : nullptr; dn = cluster_num ? h->st_num : nullptr;
     di = cluster_iters ? h->st_iters : nullptr; dr = rtn ? h->st_rtn : nullptr;
   }
   hipLaunchKernelGGL(k_emit, dim3(64, batch), dim3(256), 0, h->stream, D, batch, dv, dc, dn, di, dr);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  h->timed = e == hipSuccess;
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   if (e == hipSuccess && mem == DIRECT_MEM_HOST) {
     auto dn_ = [&](void* dst, const void* src, size_t bytes) {
       return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
@@ -1302,10 +1267,8 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
     if (e == hipSuccess) e = dn_(cluster_iters, di, (size_t)batch * 4);
     if (e == hipSuccess) e = dn_(rtn, dr, (size_t)batch * 4);
   }
-  hipError_t e2 = hipStreamSynchronize(h->stream);
-  cleanup();
-  if (e != hipSuccess || e2 != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("polygon_generation_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("polygon_generation_batch: ") + hipGetErrorString(e));
   h->resident_batch = batch;
   return DIRECT_OK;
 }
@@ -1339,14 +1302,13 @@ direct_status_t direct_cluster_convex_test(direct_cluster_handle_t h, const uint
   if (n_cluster) CHIP_TRY(hipMemcpyAsync(D.cluster, pk.data(), (size_t)n_cluster * 4, hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hipMemcpyAsync(D.el, &E, sizeof E, hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hipMemsetAsync(D.blocked, 0, (size_t)n_candidate * D.kwords * 8, h->stream));
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
   hipLaunchKernelGGL(k_flags_init, dim3(std::min((D.G + 255) / 256, 4096), 1), dim3(256), 0, h->stream, D, (const uint8_t*)h->inside_tmp);
   hipLaunchKernelGGL(k_chunk_box, dim3(D.nchunk, 1), dim3(256), 0, h->stream, D);
   hipLaunchKernelGGL(k_convex<true>, dim3(n_candidate, 1), dim3(256), 0, h->stream, D);
   hipLaunchKernelGGL(k_resolve, dim3(1), dim3(64), (size_t)D.kwords * 8, h->stream, D, 1);
   CHIP_TRY(hipGetLastError());
-  CHIP_TRY(hipEventRecord(h->ev1, h->stream));
-  h->timed = true;
+  CHIP_TRY(hs::stop(h->ev, h->stream));
   std::vector<unsigned long long> rows(can_can ? (size_t)n_candidate * D.kwords : 0);
   CHIP_TRY(hipMemcpyAsync(can_clu, D.can_clu, (size_t)n_candidate, hipMemcpyDeviceToHost, h->stream));
   if (accept) CHIP_TRY(hipMemcpyAsync(accept, D.accept, (size_t)n_candidate, hipMemcpyDeviceToHost, h->stream));
@@ -1382,55 +1344,28 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
     H.half_words = (size_t)H.QY * H.QZ + (size_t)H.QX * H.QZ + (size_t)H.QX * H.QY;
     H.line_words = 2 * H.half_words;
     // all or nothing: a failed allocation frees what this call has allocated, so that a retry starts clean
-    std::vector<void*> mine;
-    hipError_t ae = hipSuccess;
-    auto A = [&](auto pp, size_t bytes) {
-      if (ae != hipSuccess) return;
-      void* q = nullptr;
-      ae = hipMalloc(&q, bytes);
-      if (ae != hipSuccess) return;
-      mine.push_back(q);
-      *pp = (typename std::remove_pointer<decltype(pp)>::type)q;
-    };
-    A(&H.he, B * sizeof(HullElem));
-    A(&H.lines, B * H.line_words * sizeof(int));
-    A(&H.cand, B * 3 * hull::kCandCap * sizeof(int));
-    A(&H.first, B * hull::kCandCap * sizeof(int));
-    A(&H.isv, B * hull::kCandCap * sizeof(int));
-    A(&H.raw, B * hull::kRawCap * 4 * sizeof(hull::i64));
-    A(&H.sorted, B * hull::kRawCap * 4 * sizeof(hull::i64));
-    A(&H.vq, B * hull::kCandCap * 3 * sizeof(int));
+    const hipError_t ae = hs::alloc_all(h->allocs, {
+        hs::want(&H.he, B * sizeof(HullElem)), hs::want(&H.lines, B * H.line_words * sizeof(int)),
+        hs::want(&H.cand, B * 3 * hull::kCandCap * sizeof(int)), hs::want(&H.first, B * hull::kCandCap * sizeof(int)),
+        hs::want(&H.isv, B * hull::kCandCap * sizeof(int)), hs::want(&H.raw, B * hull::kRawCap * 4 * sizeof(hull::i64)),
+        hs::want(&H.sorted, B * hull::kRawCap * 4 * sizeof(hull::i64)), hs::want(&H.vq, B * hull::kCandCap * 3 * sizeof(int))});
     if (ae != hipSuccess) {
-      for (void* q : mine) (void)hipFree(q);
       H = HullDev{};
       return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: scratch allocation: ") + hipGetErrorString(ae));
     }
-    h->allocs.insert(h->allocs.end(), mine.begin(), mine.end());
     h->have_hull = true;
   }
-  // device views of the outputs: the caller's pointers, or one staging block for host outputs
+  // device views of the outputs: the caller's pointers, or slices of one staging block for host outputs (nothing is filled:
+  // the host arrays hold what the block held wherever k_hull_finish does not write)
   const size_t nb = (size_t)batch;
   const size_t sz[8] = {nb * plane_capacity * 4 * sizeof(double), nb * plane_capacity * 4 * sizeof(long long), nb * sizeof(int32_t),
                         nb * vertex_capacity * 3 * sizeof(double), nb * sizeof(int32_t), nb * 3 * sizeof(double),
                         nb * sizeof(int32_t), nb * sizeof(int32_t)};
-  void* user[8] = {planes, plane_int, n_planes, vertices, n_vertices, center, degenerate, rtn};
+  void* const user[8] = {planes, plane_int, n_planes, vertices, n_vertices, center, degenerate, rtn};
   void* dev[8];
-  if (mem == DIRECT_MEM_HOST) {
-    size_t total = 0, off[8];
-    for (int i = 0; i < 8; i++) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
-    if (total > h->hull_out_bytes) {
-      if (h->hull_out) {
-        CHIP_TRY(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->hull_out);
-        h->hull_out = nullptr; h->hull_out_bytes = 0;
-      }
-      CHIP_TRY(hipMalloc(&h->hull_out, total));
-      h->hull_out_bytes = total;
-    }
-    for (int i = 0; i < 8; i++) dev[i] = user[i] ? (char*)h->hull_out + off[i] : nullptr;
-  } else {
-    for (int i = 0; i < 8; i++) dev[i] = user[i];
-  }
+  hs::Stage st(mem == DIRECT_MEM_HOST);
+  for (int i = 0; i < 8; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
+  CHIP_TRY(hs::stage_upload(st, h->hull_out, h->stream));
   const int32_t *sx = cluster_xyz, *sn = cluster_num;
   if (cluster_xyz && mem_in == DIRECT_MEM_HOST) {  // caller-provided voxels from the host: the filled prefix of every row,
                                                    // through the generation's own staging blocks (st_xyz, st_num)
@@ -1443,7 +1378,7 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
     CHIP_TRY(hipMemcpyAsync(h->st_num, cluster_num, nb * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     sx = h->st_xyz; sn = h->st_num;
   }
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
   CHIP_TRY(hipMemset2DAsync(H.lines, H.line_words * sizeof(int), 0x7f, H.half_words * sizeof(int), nb, h->stream));
   CHIP_TRY(hipMemset2DAsync(H.lines + H.half_words, H.line_words * sizeof(int), 0x80, H.half_words * sizeof(int), nb, h->stream));
   CHIP_TRY(hipMemsetAsync(H.he, 0, nb * sizeof(HullElem), h->stream));
@@ -1455,14 +1390,9 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
                      plane_capacity, vertex_capacity, (double*)dev[0], (long long*)dev[1], (int32_t*)dev[2], (double*)dev[3],
                      (int32_t*)dev[4], (double*)dev[5], (int32_t*)dev[6], (int32_t*)dev[7]);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  h->timed = e == hipSuccess;
-  if (mem == DIRECT_MEM_HOST)
-    for (int i = 0; i < 8 && e == hipSuccess; i++)
-      if (user[i]) e = hipMemcpyAsync(user[i], dev[i], sz[i], hipMemcpyDeviceToHost, h->stream);
-  hipError_t e2 = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess || e2 != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, hs::stage_download(st, h->stream, e));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 
@@ -1484,56 +1414,29 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
     N.tx = gp::tiles_along(N.X); N.ty = gp::tiles_along(N.Y); N.tz = gp::tiles_along(N.Z);
     N.ntiles = N.tx * N.ty * N.tz;
     N.map = h->map;
-    std::vector<void*> mine;
-    hipError_t ae = hipSuccess;
-    auto A = [&](auto pp, size_t bytes) {
-      if (ae != hipSuccess) return;
-      void* q = nullptr;
-      ae = hipMalloc(&q, bytes);
-      if (ae != hipSuccess) return;
-      mine.push_back(q);
-      *pp = (typename std::remove_pointer<decltype(pp)>::type)q;
-    };
-    A(&N.field, B * (size_t)N.G * sizeof(double));
-    A(&N.flag[0], B * (size_t)N.ntiles);
-    A(&N.flag[1], B * (size_t)N.ntiles);
-    A(&N.ends, B * 6 * sizeof(int));
-    A(&N.pending, B * sizeof(int));
-    A(&N.rounds, B * sizeof(int));
-    A(&N.visits, B * sizeof(int));
-    if (ae != hipSuccess) {
-      for (void* q : mine) (void)hipFree(q);
-      return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
-    }
-    h->allocs.insert(h->allocs.end(), mine.begin(), mine.end());
+    const hipError_t ae = hs::alloc_all(h->allocs, {
+        hs::want(&N.field, B * (size_t)N.G * sizeof(double)), hs::want(&N.flag[0], B * (size_t)N.ntiles),
+        hs::want(&N.flag[1], B * (size_t)N.ntiles), hs::want(&N.ends, B * 6 * sizeof(int)), hs::want(&N.pending, B * sizeof(int)),
+        hs::want(&N.rounds, B * sizeof(int)), hs::want(&N.visits, B * sizeof(int))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
     P = N;
     h->have_path = true;
   }
-  // one block for the read-back ring and the staging of host outputs (path_xyz, path_len, path_cost, stats, rtn)
+  // one block for the read-back ring (a scratch slice, needed whatever `mem` is) and the staging of host outputs (nothing is filled)
   const size_t cap = (size_t)path_capacity;
-  const size_t sz[6] = {nb * cap * sizeof(int), nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double),
-                        nb * 2 * sizeof(int32_t), nb * sizeof(int32_t)};
-  size_t off[6], total = 0;
-  for (int i = 0; i < 6; i++) { off[i] = total; total += (sz[i] + 255) & ~(size_t)255; }
-  if (total > h->path_out_bytes) {
-    if (h->path_out) {
-      CHIP_TRY(hipStreamSynchronize(h->stream));
-      (void)hipFree(h->path_out);
-      h->path_out = nullptr; h->path_out_bytes = 0;
-    }
-    CHIP_TRY(hipMalloc(&h->path_out, total));
-    h->path_out_bytes = total;
-  }
-  P.ring = (int*)h->path_out;
-  P.cap = (int)cap;
-  void* user[5] = {path_xyz, path_len, path_cost, stats, rtn};
+  const size_t sz[5] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t)};
+  void* const user[5] = {path_xyz, path_len, path_cost, stats, rtn};
   void* dev[5];
-  for (int i = 0; i < 5; i++) dev[i] = mem == DIRECT_MEM_HOST ? (user[i] ? (char*)h->path_out + off[i + 1] : nullptr) : user[i];
+  hs::Stage st(mem == DIRECT_MEM_HOST);
+  hs::stage_scratch(st, &P.ring, nb * cap * sizeof(int));
+  for (int i = 0; i < 5; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
+  CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
+  P.cap = (int)cap;
   std::vector<int> ends(nb * 6);
   for (size_t b = 0; b < nb; b++)
     for (int a = 0; a < 3; a++) { ends[6 * b + a] = starts[3 * b + a]; ends[6 * b + 3 + a] = goals[3 * b + a]; }
   CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
   hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
   CHIP_TRY(hipGetLastError());
   // Rounds are separate launches, enqueued blindly kRoundsPerCheck at a time (a workgroup whose tile is not active returns at
@@ -1556,35 +1459,15 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
   hipLaunchKernelGGL(k_path_trace, dim3(batch), dim3(64), 0, h->stream, P, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
                      (int32_t*)dev[3], (int32_t*)dev[4]);
   hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  h->timed = e == hipSuccess;
-  if (mem == DIRECT_MEM_HOST)
-    for (int i = 0; i < 5 && e == hipSuccess; i++)
-      if (user[i]) e = hipMemcpyAsync(user[i], dev[i], sz[i + 1], hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(st, h->stream, e);
   if (e == hipSuccess && dist)
     e = hipMemcpyAsync(dist, P.field, nb * (size_t)P.G * sizeof(double),
                        mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
-  hipError_t e2 = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess || e2 != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
-
-namespace {
-// one device block of at least `bytes`, kept in the handle and regrown (after the stream has drained) when a call needs more
-hipError_t plan_grow(direct_cluster_handle_t h, void** buf, size_t* have, size_t bytes) {
-  if (bytes <= *have) return hipSuccess;
-  if (*buf) {
-    hipError_t e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return e;
-    (void)hipFree(*buf);
-    *buf = nullptr; *have = 0;
-  }
-  hipError_t e = hipMalloc(buf, bytes);
-  if (e == hipSuccess) *have = bytes;
-  return e;
-}
-}  // namespace
 
 direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in, direct_plan_check_out_t* out) {
   if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return cfail(DIRECT_ERR_INVALID, "null argument");
@@ -1603,13 +1486,12 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
   if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const Dev& D = h->D;
-  const bool host = in->mem == DIRECT_MEM_HOST;
   const size_t r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
   auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   // workspace: counters, S, per-slot leaves, unresolved list
   const size_t w_S = up(256), w_first = w_S + up(B * (nm + 1) * sizeof(double)), w_list = w_first + up(slots * sizeof(int)),
                w_total = w_list + up(slots * sizeof(int));
-  CHIP_TRY(plan_grow(h, &h->plan_ws, &h->plan_ws_bytes, w_total));
+  CHIP_TRY(hs::grow(h->plan_ws, h->stream, w_total));
   PlanDev A = {};
   for (int a = 0; a < 3; a++) A.G.lower[a] = in->map_lower[a];
   A.G.inv = 1.0 / in->resolution;
@@ -1618,44 +1500,32 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
   A.G.outside_blocks = in->outside_blocks;
   A.batch = in->batch; A.nmax = in->n_seg_max; A.depth = in->depth; A.poly = in->poly != nullptr; A.has_from = in->t_from != nullptr;
   A.count = out->stats != nullptr;
-  char* W = (char*)h->plan_ws;
+  char* W = (char*)h->plan_ws.p;
   A.n_list = (unsigned*)W; A.n_tests = (unsigned long long*)(W + 8);
   A.S = (double*)(W + w_S); A.ws_first = (int*)(W + w_first); A.list = (int*)(W + w_list);
-  const void* coef = in->poly ? in->poly : in->bez;
-  // host arrays go through one staging block: n_seg, T, coef, t_from in; the six outputs back
-  const void* src[4] = {in->n_seg, in->T, coef, in->t_from};
-  void* user[6] = {out->status, out->verdict, out->t_free, out->first, out->hit_box, out->seg_first};
-  const size_t isz[4] = {B * 4, slots * r, slots * 18 * r, B * 8}, osz[6] = {B * 4, B * 4, B * 8, B * 8, B * 24, slots * 4};
-  void* dev_in[4] = {(void*)in->n_seg, (void*)in->T, (void*)coef, (void*)in->t_from};
-  void* dev_out[6] = {user[0], user[1], user[2], user[3], user[4], user[5]};
-  if (host) {
-    size_t total = 0, ioff[4], ooff[6];
-    for (int i = 0; i < 4; i++) { ioff[i] = total; total += up(isz[i]); }
-    for (int i = 0; i < 6; i++) { ooff[i] = total; total += up(osz[i]); }
-    CHIP_TRY(plan_grow(h, &h->plan_io, &h->plan_io_bytes, total));
-    for (int i = 0; i < 4; i++) {
-      dev_in[i] = src[i] ? (char*)h->plan_io + ioff[i] : nullptr;
-      if (src[i]) CHIP_TRY(hipMemcpyAsync(dev_in[i], src[i], isz[i], hipMemcpyHostToDevice, h->stream));
-    }
-    for (int i = 0; i < 6; i++) dev_out[i] = user[i] ? (char*)h->plan_io + ooff[i] : nullptr;
-    if (dev_out[5]) CHIP_TRY(hipMemsetAsync(dev_out[5], 0xff, osz[5], h->stream));  // entries past n_seg read -1
-  }
-  A.n_seg = (const int32_t*)dev_in[0]; A.T = dev_in[1]; A.coef = dev_in[2]; A.t_from = (const double*)dev_in[3];
-  A.status = (int32_t*)dev_out[0]; A.verdict = (int32_t*)dev_out[1]; A.t_free = (double*)dev_out[2]; A.first = (int32_t*)dev_out[3];
-  A.hit_box = (int32_t*)dev_out[4]; A.seg_first = (int32_t*)dev_out[5];
-  CHIP_TRY(hipEventRecord(h->ev0, h->stream));
-  hipError_t e = hipMemsetAsync(h->plan_ws, 0, 16, h->stream);
+  // host arrays go through one staging block: n_seg, T, coef, t_from in; the six outputs back, of which seg_first alone is
+  // filled (0xff: entries past n_seg read -1)
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &A.T, in->T, slots * r);
+  hs::stage_in(st, &A.coef, in->poly ? in->poly : in->bez, slots * 18 * r);
+  hs::stage_in(st, &A.t_from, in->t_from, B * 8);
+  hs::stage_out(st, &A.status, out->status, B * 4);
+  hs::stage_out(st, &A.verdict, out->verdict, B * 4);
+  hs::stage_out(st, &A.t_free, out->t_free, B * 8);
+  hs::stage_out(st, &A.first, out->first, B * 8);
+  hs::stage_out(st, &A.hit_box, out->hit_box, B * 24);
+  hs::stage_out(st, &A.seg_first, out->seg_first, slots * 4, 0xff);
+  CHIP_TRY(hs::stage_upload(st, h->plan_io, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(h->plan_ws.p, 0, 16, h->stream);
   if (e == hipSuccess) e = in->dtype == DIRECT_F32 ? plan_check_launch<float>(D, A, h->stream) : plan_check_launch<double>(D, A, h->stream);
-  if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-  h->timed = e == hipSuccess;
-  if (host)
-    for (int i = 0; i < 6 && e == hipSuccess; i++)
-      if (user[i]) e = hipMemcpyAsync(user[i], dev_out[i], osz[i], hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(st, h->stream, e);
   unsigned long long cnt[2] = {0, 0};
-  if (e == hipSuccess && out->stats) e = hipMemcpyAsync(cnt, h->plan_ws, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
-  hipError_t e2 = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess || e2 != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("plan_check_batch: ") + hipGetErrorString(e != hipSuccess ? e : e2));
+  if (e == hipSuccess && out->stats) e = hipMemcpyAsync(cnt, h->plan_ws.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_check_batch: ") + hipGetErrorString(e));
   if (out->stats) { out->stats[0] = (int64_t)(cnt[0] & 0xffffffffull); out->stats[1] = (int64_t)cnt[1]; }
   return DIRECT_OK;
 }
@@ -1668,9 +1538,8 @@ direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_s
 
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms) {
   if (!h || !ms) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->timed) return cfail(DIRECT_ERR_INVALID, "nothing has been timed yet");
-  CHIP_TRY(hipEventSynchronize(h->ev1));
-  CHIP_TRY(hipEventElapsedTime(ms, h->ev0, h->ev1));
+  if (!h->ev.timed) return cfail(DIRECT_ERR_INVALID, "nothing has been timed yet");
+  CHIP_TRY(hs::elapsed(h->ev, ms));
   return DIRECT_OK;
 }
 

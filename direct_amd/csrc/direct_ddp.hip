@@ -19,6 +19,7 @@
 #include "traj_eval.h"
 #include "traj_audit.h"
 #include "corridor_io.h"
+#include "host_stage.h"
 #include "rccl_gather.h"
 
 using namespace direct;
@@ -503,16 +504,14 @@ struct direct_ddp_handle_s {
   hipEvent_t cev[12] = {}, fork_ev = nullptr;
   size_t rsz = 4;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
-  bool sample_timed = false;
-  hipEvent_t eval_ev0 = nullptr, eval_ev1 = nullptr;  // direct_traj_eval_last_ms
-  bool eval_timed = false;
-  double* eval_S = nullptr;  // segment start times of the last direct_traj_eval_batch [batch][n_seg_max + 1] (grown on demand)
-  size_t eval_S_bytes = 0;
-  hipEvent_t audit_ev0 = nullptr, audit_ev1 = nullptr;  // direct_traj_audit_last_ms
-  bool audit_timed = false;
-  char* audit_ws = nullptr;  // segment start times, per-segment records and verdicts of the last direct_traj_audit_batch (grown on demand)
-  size_t audit_ws_bytes = 0;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hs::EventPair sample_ev, eval_ev, audit_ev;  // direct_traj_{sample,eval,audit}_last_ms
+  hs::Block eval_S;    // segment start times of the last direct_traj_eval_batch [batch][n_seg_max + 1] (grown on demand)
+  hs::Block audit_ws;  // segment start times, per-segment records and verdicts of the last direct_traj_audit_batch (grown on demand)
+  // Host arrays of sample / eval / audit are staged through this ONE block: a host-memory call drains the stream before it
+  // returns, so the block is idle when the next call lays its arrays out.  The two workspaces above stay apart: device-memory
+  // calls are asynchronous and their kernels outlive the call.
+  hs::Block stage;
   int n_launches = 0;
   bool timed = false;
   // device buffers
@@ -594,11 +593,8 @@ struct direct_ddp_handle_s {
 
 template <typename T>
 static direct_status_t dalloc(direct_ddp_handle_t h, T** p, size_t bytes) {
-  void* q = nullptr;
-  hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+  hipError_t e = hs::alloc_all(h->allocs, {hs::want(p, bytes)});
   if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  h->allocs.push_back(q);
-  *p = (T*)q;
   return DIRECT_OK;
 }
 #define TRY(expr)                            \
@@ -920,246 +916,123 @@ static void launch_finish_t(direct_ddp_handle_t h, const direct_ddp_batch_out_t*
   }
 }
 
-// direct_traj_sample_batch for one storage type: host arrays are staged through temporary device buffers
+// sample / eval / audit: host arrays go through the handle's staging block (hs::Stage, host_stage.h), device arrays are passed
+// through.  Staged outputs are zero-filled: whatever the kernels leave unwritten (entries past `count`, past n_query, past n_seg)
+// then reads 0 on the host; device-resident outputs are left untouched there.
+static direct_status_t staged_upload(direct_ddp_handle_t h, hs::Stage& st, const char* name) {
+  const hipError_t e = hs::stage_upload(st, h->stage, h->stream);
+  return e == hipSuccess ? DIRECT_OK : fail(DIRECT_ERR_DEVICE, std::string(name) + ": staging: " + hipGetErrorString(e));
+}
+// after the launches: host outputs back and the stream drained; a device-memory call stays asynchronous
+static direct_status_t staged_finish(direct_ddp_handle_t h, const hs::Stage& st, const char* name) {
+  hipError_t e = hs::stage_download(st, h->stream, hipGetLastError());
+  if (st.host) e = hs::drain(h->stream, e);
+  return e == hipSuccess ? DIRECT_OK : fail(DIRECT_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
+}
+// a workspace the handle owns, grown on demand (its previous users are waited for before the old block is freed)
+static direct_status_t workspace(direct_ddp_handle_t h, hs::Block& ws, size_t bytes, const char* name) {
+  const hipError_t e = hs::grow(ws, h->stream, bytes);
+  return e == hipSuccess ? DIRECT_OK : fail(DIRECT_ERR_DEVICE, std::string("workspace of ") + name + ": " + hipGetErrorString(e));
+}
+
 template <typename Real>
 static direct_status_t sample_t(direct_ddp_handle_t h, const direct_sample_in_t* in, direct_sample_out_t* out) {
   const size_t B = in->batch, nm = in->n_seg_max, cap = in->capacity, r = sizeof(Real);
-  const bool host = in->mem == DIRECT_MEM_HOST;
   SampleArgs<Real> A;
   A.batch = in->batch; A.nmax = in->n_seg_max; A.capacity = in->capacity; A.derivs = in->derivs; A.dt = in->dt; A.inv_dt = 1.0 / in->dt;
-  std::vector<void*> tmp;
-  auto dev = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    tmp.push_back(q);
-    return q;
-  };
-  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
-  auto in_arr = [&](const void* src, size_t bytes) -> const void* {
-    if (!host) return src;
-    void* q = dev(bytes);
-    if (q && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
-    return q;
-  };
-  // staged outputs are zero-filled: entries past `count` then read 0 on the host (device-resident
-  // output arrays are left untouched past `count`)
-  auto out_arr = [&](void* dst, size_t bytes) -> void* {
-    if (!host || !dst) return dst;
-    void* q = dev(bytes);
-    if (q && hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) return nullptr;
-    return q;
-  };
-  A.n_seg = (const int32_t*)in_arr(in->n_seg, B * 4);
-  A.bez = (const Real*)in_arr(in->bez, B * nm * 18 * r);
-  A.T = (const Real*)in_arr(in->T, B * nm * r);
-  A.count = (int32_t*)out_arr(out->count, B * 4);
-  A.seg_first = (int32_t*)out_arr(out->seg_first, B * nm * 4);
-  A.pos = (Real*)out_arr(out->pos, B * cap * 3 * r);
-  A.vel = (Real*)out_arr(out->vel, B * cap * 3 * r);
-  A.acc = (Real*)out_arr(out->acc, B * cap * 3 * r);
-  A.length = (Real*)out_arr(out->length, B * r);
-  A.vmax = (Real*)out_arr(out->vmax, B * r);
-  A.amax = (Real*)out_arr(out->amax, B * r);
-  A.cmax = (Real*)out_arr(out->cmax, B * r);
   A.pmax = in->p_max;
-  A.n_planes = out->cmax ? (const int32_t*)in_arr(in->n_planes, B * nm * 4) : nullptr;
-  A.planes = out->cmax ? (const Real*)in_arr(in->planes, B * nm * (size_t)in->p_max * 4 * r) : nullptr;
-  if (out->cmax && (!A.n_planes || !A.planes || !A.cmax)) {
-    cleanup();
-    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_sample_batch");
-  }
-  if (!A.n_seg || !A.bez || !A.T || !A.count || !A.pos || (out->vel && !A.vel) || (out->acc && !A.acc)) {
-    cleanup();
-    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_sample_batch");
-  }
-  (void)hipEventRecord(h->ev2, h->stream);
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &A.bez, in->bez, B * nm * 18 * r);
+  hs::stage_in(st, &A.T, in->T, B * nm * r);
+  hs::stage_in(st, &A.n_planes, out->cmax ? in->n_planes : nullptr, B * nm * 4);  // the corridor is read for cmax only
+  hs::stage_in(st, &A.planes, out->cmax ? in->planes : nullptr, B * nm * (size_t)in->p_max * 4 * r);
+  hs::stage_out(st, &A.count, out->count, B * 4, 0);
+  hs::stage_out(st, &A.seg_first, out->seg_first, B * nm * 4, 0);
+  hs::stage_out(st, &A.pos, out->pos, B * cap * 3 * r, 0);
+  hs::stage_out(st, &A.vel, out->vel, B * cap * 3 * r, 0);
+  hs::stage_out(st, &A.acc, out->acc, B * cap * 3 * r, 0);
+  hs::stage_out(st, &A.length, out->length, B * r, 0);
+  hs::stage_out(st, &A.vmax, out->vmax, B * r, 0);
+  hs::stage_out(st, &A.amax, out->amax, B * r, 0);
+  hs::stage_out(st, &A.cmax, out->cmax, B * r, 0);
+  TRY(staged_upload(h, st, "direct_traj_sample_batch"));
+  (void)hs::start(h->sample_ev, h->stream);
   hipLaunchKernelGGL(k_sample<Real>, dim3(in->batch), dim3(64), 0, h->stream, A);
-  (void)hipEventRecord(h->ev3, h->stream);
-  h->sample_timed = true;
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && host) {
-    auto dn = [&](void* dst, const void* src, size_t bytes) {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
-    if (e == hipSuccess) e = dn(out->count, A.count, B * 4);
-    if (e == hipSuccess) e = dn(out->seg_first, A.seg_first, B * nm * 4);
-    if (e == hipSuccess) e = dn(out->pos, A.pos, B * cap * 3 * r);
-    if (e == hipSuccess) e = dn(out->vel, A.vel, B * cap * 3 * r);
-    if (e == hipSuccess) e = dn(out->acc, A.acc, B * cap * 3 * r);
-    if (e == hipSuccess) e = dn(out->length, A.length, B * r);
-    if (e == hipSuccess) e = dn(out->vmax, A.vmax, B * r);
-    if (e == hipSuccess) e = dn(out->amax, A.amax, B * r);
-    if (e == hipSuccess) e = dn(out->cmax, A.cmax, B * r);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  }
-  if (host) { (void)hipStreamSynchronize(h->stream); cleanup(); }
-  if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("direct_traj_sample_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  (void)hs::stop(h->sample_ev, h->stream);
+  return staged_finish(h, st, "direct_traj_sample_batch");
 }
 
-// direct_traj_eval_batch for one storage type: host arrays are staged through temporary device buffers as in sample_t
 template <typename Real>
 static direct_status_t eval_t(direct_ddp_handle_t h, const direct_eval_in_t* in, direct_eval_out_t* out) {
   const size_t B = in->batch, nm = in->n_seg_max, M = in->m_max, r = sizeof(Real);
-  const bool host = in->mem == DIRECT_MEM_HOST;
-  const size_t s_bytes = B * (nm + 1) * sizeof(double);
-  if (h->eval_S_bytes < s_bytes) {  // hipFree waits for the kernels that still read the old workspace
-    if (h->eval_S) (void)hipFree(h->eval_S);
-    h->eval_S = nullptr;
-    h->eval_S_bytes = 0;
-    if (hipMalloc((void**)&h->eval_S, s_bytes) != hipSuccess) {
-      h->eval_S = nullptr;
-      return fail(DIRECT_ERR_DEVICE, "workspace of direct_traj_eval_batch");
-    }
-    h->eval_S_bytes = s_bytes;
-  }
-  std::vector<void*> tmp;
-  auto dev = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    tmp.push_back(q);
-    return q;
-  };
-  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
-  auto in_arr = [&](const void* src, size_t bytes) -> const void* {
-    if (!host || !src) return src;
-    void* q = dev(bytes);
-    if (q && hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) return nullptr;
-    return q;
-  };
-  // staged outputs are zero-filled: entries past n_query then read 0 on the host (device-resident outputs are left untouched)
-  auto out_arr = [&](void* dst, size_t bytes) -> void* {
-    if (!host || !dst) return dst;
-    void* q = dev(bytes);
-    if (q && hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) return nullptr;
-    return q;
-  };
+  TRY(workspace(h, h->eval_S, B * (nm + 1) * sizeof(double), "direct_traj_eval_batch"));
   EvalArgs<Real> A;
   A.batch = in->batch; A.nmax = in->n_seg_max; A.m_max = in->m_max; A.poly = in->poly != nullptr; A.b_off = 0;
-  A.t0 = in->t0; A.dt = in->dt; A.S = h->eval_S;
-  A.n_seg = (const int32_t*)in_arr(in->n_seg, B * 4);
-  A.T = (const Real*)in_arr(in->T, B * nm * r);
-  A.coef = (const Real*)in_arr(A.poly ? in->poly : in->bez, B * nm * 18 * r);
-  A.n_query = (const int32_t*)in_arr(in->n_query, B * 4);
-  A.t = (const Real*)in_arr(in->t, B * M * r);
-  A.status = (int32_t*)out_arr(out->status, B * 4);
-  A.t_total = (Real*)out_arr(out->t_total, B * r);
-  A.seg = (int32_t*)out_arr(out->seg, B * M * 4);
+  A.t0 = in->t0; A.dt = in->dt; A.S = (double*)h->eval_S.p;
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &A.T, in->T, B * nm * r);
+  hs::stage_in(st, &A.coef, A.poly ? in->poly : in->bez, B * nm * 18 * r);
+  hs::stage_in(st, &A.n_query, in->n_query, B * 4);
+  hs::stage_in(st, &A.t, in->t, B * M * r);
+  hs::stage_out(st, &A.status, out->status, B * 4, 0);
+  hs::stage_out(st, &A.t_total, out->t_total, B * r, 0);
+  hs::stage_out(st, &A.seg, out->seg, B * M * 4, 0);
   void* const outs[5] = {out->pos, out->vel, out->acc, out->jerk, out->snap};
-  bool ok = A.n_seg && A.T && A.coef && A.status && (A.n_query || !in->n_query) && (A.t || !in->t) &&
-            (A.t_total || !out->t_total) && (A.seg || !out->seg);
-  for (int k = 0; k < 5; k++) {
-    A.out[k] = (Real*)out_arr(outs[k], B * M * 3 * r);
-    ok = ok && (A.out[k] || !outs[k]);
-  }
-  A.state = (Real*)out_arr(out->state, B * M * 9 * r);
-  ok = ok && (A.state || !out->state);
-  if (!ok) {
-    cleanup();
-    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_eval_batch");
-  }
+  for (int k = 0; k < 5; k++) hs::stage_out(st, &A.out[k], outs[k], B * M * 3 * r, 0);
+  hs::stage_out(st, &A.state, out->state, B * M * 9 * r, 0);
+  TRY(staged_upload(h, st, "direct_traj_eval_batch"));
   const int chunks = (int)((M + kEvalChunk - 1) / kEvalChunk);
   // the workspace S belongs to the handle: a call waits for the previous call's k_eval, on whichever stream that ran
-  if (h->eval_timed) (void)hipStreamWaitEvent(h->stream, h->eval_ev1, 0);
-  (void)hipEventRecord(h->eval_ev0, h->stream);
+  if (h->eval_ev.timed) (void)hipStreamWaitEvent(h->stream, h->eval_ev.ev1, 0);
+  (void)hs::start(h->eval_ev, h->stream);
   hipLaunchKernelGGL(k_eval_starts<Real>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, A);
   for (int b0 = 0; b0 < in->batch; b0 += 65535) {  // gridDim.y is 16-bit
     A.b_off = b0;
     hipLaunchKernelGGL(k_eval<Real>, dim3(chunks, std::min(65535, in->batch - b0)), dim3(64), eval_lds_bytes(in->n_seg_max),
                        h->stream, A);
   }
-  (void)hipEventRecord(h->eval_ev1, h->stream);
-  h->eval_timed = true;
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && host) {
-    auto dn = [&](void* dst, const void* src, size_t bytes) {
-      return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream) : hipSuccess;
-    };
-    if (e == hipSuccess) e = dn(out->status, A.status, B * 4);
-    if (e == hipSuccess) e = dn(out->t_total, A.t_total, B * r);
-    if (e == hipSuccess) e = dn(out->seg, A.seg, B * M * 4);
-    for (int k = 0; k < 5; k++)
-      if (e == hipSuccess) e = dn(outs[k], A.out[k], B * M * 3 * r);
-    if (e == hipSuccess) e = dn(out->state, A.state, B * M * 9 * r);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  }
-  if (host) { (void)hipStreamSynchronize(h->stream); cleanup(); }
-  if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("direct_traj_eval_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  (void)hs::stop(h->eval_ev, h->stream);
+  return staged_finish(h, st, "direct_traj_eval_batch");
 }
 
-// direct_traj_audit_batch for one storage type: host arrays are staged through temporary device buffers as in eval_t
 template <typename Real>
 static direct_status_t audit_t(direct_ddp_handle_t h, const direct_audit_in_t* in, direct_audit_out_t* out) {
   const size_t B = in->batch, nm = in->n_seg_max, r = sizeof(Real);
-  const bool host = in->mem == DIRECT_MEM_HOST, planes = in->planes != nullptr;
+  const bool planes = in->planes != nullptr;
   const size_t pm = planes ? in->p_max : 0;
-  const size_t ws_bytes = audit_ws_bytes(B, nm);
-  if (h->audit_ws_bytes < ws_bytes) {  // hipFree waits for the kernels that still use the old workspace
-    if (h->audit_ws) (void)hipFree(h->audit_ws);
-    h->audit_ws = nullptr;
-    h->audit_ws_bytes = 0;
-    if (hipMalloc((void**)&h->audit_ws, ws_bytes) != hipSuccess) {
-      h->audit_ws = nullptr;
-      return fail(DIRECT_ERR_DEVICE, "workspace of direct_traj_audit_batch");
-    }
-    h->audit_ws_bytes = ws_bytes;
-  }
-  std::vector<void*> tmp;
-  bool ok = true;
-  auto dev = [&](size_t bytes) -> void* {
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    tmp.push_back(q);
-    return q;
-  };
-  auto cleanup = [&]() { for (void* q : tmp) (void)hipFree(q); };
-  auto in_arr = [&](const void* src, size_t bytes) -> const void* {
-    if (!host || !src) return src;
-    void* q = dev(bytes);
-    if (!q || hipMemcpyAsync(q, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ok = false;
-    return q;
-  };
-  // staged outputs are zero-filled: seg_peak entries past n_seg then read 0 on the host (device-resident outputs are left untouched)
-  auto out_arr = [&](void* dst, size_t bytes) -> void* {
-    if (!host || !dst) return dst;
-    void* q = dev(bytes);
-    if (!q || hipMemsetAsync(q, 0, bytes, h->stream) != hipSuccess) ok = false;
-    return q;
-  };
+  TRY(workspace(h, h->audit_ws, audit_ws_bytes(B, nm), "direct_traj_audit_batch"));
   AuditArgs<Real> A;
   A.batch = in->batch; A.nmax = in->n_seg_max; A.pmax = (int)pm; A.poly = in->poly != nullptr; A.has_planes = planes;
   A.norms = out->vnorm || out->anorm || out->jnorm || in->limit_on_norm;
   A.lim = audit::Limits{in->max_vel, in->max_acc, in->max_jerk, in->clearance, in->limit_on_norm, planes};
-  A.S = (double*)h->audit_ws;
+  A.S = (double*)h->audit_ws.p;
   A.W = A.S + B * (nm + 1);
   A.V = (int32_t*)(A.W + B * nm * audit::kWs);
-  A.n_seg = (const int32_t*)in_arr(in->n_seg, B * 4);
-  A.T = (const Real*)in_arr(in->T, B * nm * r);
-  A.coef = (const Real*)in_arr(A.poly ? in->poly : in->bez, B * nm * 18 * r);
-  A.n_planes = (const int32_t*)in_arr(in->n_planes, B * nm * 4);
-  A.planes = (const Real*)in_arr(in->planes, B * nm * pm * 4 * r);
-  A.cost = (const Real*)in_arr(in->cost, B * r);
-  A.rtn = (const int32_t*)in_arr(in->rtn, B * 4);
-  A.status = (int32_t*)out_arr(out->status, B * 4);
-  A.t_total = (Real*)out_arr(out->t_total, B * r);
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &A.T, in->T, B * nm * r);
+  hs::stage_in(st, &A.coef, A.poly ? in->poly : in->bez, B * nm * 18 * r);
+  hs::stage_in(st, &A.n_planes, in->n_planes, B * nm * 4);
+  hs::stage_in(st, &A.planes, in->planes, B * nm * pm * 4 * r);
+  hs::stage_in(st, &A.cost, in->cost, B * r);
+  hs::stage_in(st, &A.rtn, in->rtn, B * 4);
+  hs::stage_out(st, &A.status, out->status, B * 4, 0);
+  hs::stage_out(st, &A.t_total, out->t_total, B * r, 0);
   void* const peaks[7] = {out->vpeak, out->apeak, out->jpeak, out->vnorm, out->anorm, out->jnorm, out->cpeak};
-  for (int k = 0; k < 7; k++) A.peak[k] = (Real*)out_arr(peaks[k], B * r);
-  A.c_where = (int32_t*)out_arr(out->c_where, B * 2 * 4);
-  A.at = (Real*)out_arr(out->at, B * 4 * r);
-  A.seg_peak = (Real*)out_arr(out->seg_peak, B * nm * 4 * r);
-  A.gap = (Real*)out_arr(out->gap, B * 3 * r);
-  A.verdict = (int32_t*)out_arr(out->verdict, B * 4);
-  A.slowdown = (Real*)out_arr(out->slowdown, B * r);
-  A.best = (long long*)out_arr(out->best, 8);
-  if (!ok) {
-    if (host) (void)hipStreamSynchronize(h->stream);
-    cleanup();
-    return fail(DIRECT_ERR_DEVICE, "staging buffers for direct_traj_audit_batch");
-  }
+  for (int k = 0; k < 7; k++) hs::stage_out(st, &A.peak[k], peaks[k], B * r, 0);
+  hs::stage_out(st, &A.c_where, out->c_where, B * 2 * 4, 0);
+  hs::stage_out(st, &A.at, out->at, B * 4 * r, 0);
+  hs::stage_out(st, &A.seg_peak, out->seg_peak, B * nm * 4 * r, 0);
+  hs::stage_out(st, &A.gap, out->gap, B * 3 * r, 0);
+  hs::stage_out(st, &A.verdict, out->verdict, B * 4, 0);
+  hs::stage_out(st, &A.slowdown, out->slowdown, B * r, 0);
+  hs::stage_out(st, &A.best, out->best, 8, 0);
+  TRY(staged_upload(h, st, "direct_traj_audit_batch"));
   // the workspace belongs to the handle: a call waits for the previous call's kernels, on whichever stream they ran
-  if (h->audit_timed) (void)hipStreamWaitEvent(h->stream, h->audit_ev1, 0);
-  (void)hipEventRecord(h->audit_ev0, h->stream);
+  if (h->audit_ev.timed) (void)hipStreamWaitEvent(h->stream, h->audit_ev.ev1, 0);
+  (void)hs::start(h->audit_ev, h->stream);
   hipLaunchKernelGGL(k_audit_starts<Real>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, h->stream, A);
   const unsigned waves = (unsigned)((B * nm + kAuditSeg - 1) / kAuditSeg);
   if (A.poly)
@@ -1168,28 +1041,8 @@ static direct_status_t audit_t(direct_ddp_handle_t h, const direct_audit_in_t* i
     hipLaunchKernelGGL((k_audit_items<false, Real>), dim3(waves), dim3(64), 0, h->stream, A);
   hipLaunchKernelGGL(k_audit_rows<Real>, dim3((unsigned)B), dim3(64), 0, h->stream, A);
   if (A.best) hipLaunchKernelGGL(k_audit_best<Real>, dim3(1), dim3(256), 0, h->stream, A);
-  (void)hipEventRecord(h->audit_ev1, h->stream);
-  h->audit_timed = true;
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && host) {
-    auto dn = [&](void* dst, const void* src, size_t bytes) {
-      if (dst && e == hipSuccess) e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream);
-    };
-    dn(out->status, A.status, B * 4);
-    dn(out->t_total, A.t_total, B * r);
-    for (int k = 0; k < 7; k++) dn(peaks[k], A.peak[k], B * r);
-    dn(out->c_where, A.c_where, B * 2 * 4);
-    dn(out->at, A.at, B * 4 * r);
-    dn(out->seg_peak, A.seg_peak, B * nm * 4 * r);
-    dn(out->gap, A.gap, B * 3 * r);
-    dn(out->verdict, A.verdict, B * 4);
-    dn(out->slowdown, A.slowdown, B * r);
-    dn(out->best, A.best, 8);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-  }
-  if (host) { (void)hipStreamSynchronize(h->stream); cleanup(); }
-  if (e != hipSuccess) return fail(DIRECT_ERR_DEVICE, std::string("direct_traj_audit_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  (void)hs::stop(h->audit_ev, h->stream);
+  return staged_finish(h, st, "direct_traj_audit_batch");
 }
 
 extern "C" {
@@ -1331,9 +1184,8 @@ direct_status_t direct_ddp_create(const direct_ddp_config_t* cfg, direct_ddp_han
   h->fieldbuf_bytes = B * nm * (size_t)std::max(ncm, 100) * r + B * 16 * r + B * 9 * r;
   A(&h->fieldbuf, h->fieldbuf_bytes);
   if (st == DIRECT_OK && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess ||
-                          hipEventCreate(&h->ev2) != hipSuccess || hipEventCreate(&h->ev3) != hipSuccess ||
-                          hipEventCreate(&h->eval_ev0) != hipSuccess || hipEventCreate(&h->eval_ev1) != hipSuccess ||
-                          hipEventCreate(&h->audit_ev0) != hipSuccess || hipEventCreate(&h->audit_ev1) != hipSuccess))
+                          hs::create(h->sample_ev) != hipSuccess || hs::create(h->eval_ev) != hipSuccess ||
+                          hs::create(h->audit_ev) != hipSuccess))
     st = fail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
   if (st == DIRECT_OK && hipMemset(h->sched, 0, (B + 2) * sizeof(int)) != hipSuccess)
     st = fail(DIRECT_ERR_DEVICE, "hipMemset failed");
@@ -1366,14 +1218,8 @@ direct_status_t direct_ddp_destroy(direct_ddp_handle_t h) {
   if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->ev2) (void)hipEventDestroy(h->ev2);
-  if (h->ev3) (void)hipEventDestroy(h->ev3);
-  if (h->eval_ev0) (void)hipEventDestroy(h->eval_ev0);
-  if (h->eval_ev1) (void)hipEventDestroy(h->eval_ev1);
-  if (h->eval_S) (void)hipFree(h->eval_S);
-  if (h->audit_ev0) (void)hipEventDestroy(h->audit_ev0);
-  if (h->audit_ev1) (void)hipEventDestroy(h->audit_ev1);
-  if (h->audit_ws) (void)hipFree(h->audit_ws);
+  for (hs::EventPair* t : {&h->sample_ev, &h->eval_ev, &h->audit_ev}) hs::destroy(*t);
+  for (hs::Block* b : {&h->eval_S, &h->audit_ws, &h->stage}) hs::release(*b);
   delete h;
   return DIRECT_OK;
 }
@@ -2077,9 +1923,8 @@ direct_status_t direct_traj_sample_batch(direct_ddp_handle_t h, const direct_sam
 
 direct_status_t direct_traj_sample_last_ms(direct_ddp_handle_t h, float* ms) {
   if (!h || !ms) return fail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->sample_timed) return fail(DIRECT_ERR_INVALID, "no sampling launch to time");
-  HIP_TRY(hipEventSynchronize(h->ev3));
-  HIP_TRY(hipEventElapsedTime(ms, h->ev2, h->ev3));
+  if (!h->sample_ev.timed) return fail(DIRECT_ERR_INVALID, "no sampling launch to time");
+  HIP_TRY(hs::elapsed(h->sample_ev, ms));
   return DIRECT_OK;
 }
 
@@ -2098,9 +1943,8 @@ direct_status_t direct_traj_eval_batch(direct_ddp_handle_t h, const direct_eval_
 
 direct_status_t direct_traj_eval_last_ms(direct_ddp_handle_t h, float* ms) {
   if (!h || !ms) return fail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->eval_timed) return fail(DIRECT_ERR_INVALID, "no evaluation launch to time");
-  HIP_TRY(hipEventSynchronize(h->eval_ev1));
-  HIP_TRY(hipEventElapsedTime(ms, h->eval_ev0, h->eval_ev1));
+  if (!h->eval_ev.timed) return fail(DIRECT_ERR_INVALID, "no evaluation launch to time");
+  HIP_TRY(hs::elapsed(h->eval_ev, ms));
   return DIRECT_OK;
 }
 
@@ -2124,9 +1968,8 @@ direct_status_t direct_traj_audit_batch(direct_ddp_handle_t h, const direct_audi
 
 direct_status_t direct_traj_audit_last_ms(direct_ddp_handle_t h, float* ms) {
   if (!h || !ms) return fail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->audit_timed) return fail(DIRECT_ERR_INVALID, "no audit launch to time");
-  HIP_TRY(hipEventSynchronize(h->audit_ev1));
-  HIP_TRY(hipEventElapsedTime(ms, h->audit_ev0, h->audit_ev1));
+  if (!h->audit_ev.timed) return fail(DIRECT_ERR_INVALID, "no audit launch to time");
+  HIP_TRY(hs::elapsed(h->audit_ev, ms));
   return DIRECT_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/direct_quad.h"
+#include "host_stage.h"
 
 namespace {
 
@@ -565,14 +566,14 @@ direct_status_t qfail(direct_status_t st, const std::string& msg) {
 struct direct_quad_handle_s {
   int dtype = 0, device = 0, max_batch = 0, N = 0, B = 0;
   size_t rsz = 4;
-  bool begun = false, timed = false;
+  bool begun = false;
   void *x0 = nullptr, *xg = nullptr, *X[2] = {nullptr, nullptr}, *U[2] = {nullptr, nullptr}, *K = nullptr, *kf = nullptr, *Tg[2] = {nullptr, nullptr};
   void *o_cost = nullptr, *o_x = nullptr, *o_u = nullptr;
   int32_t* o_iters = nullptr;
   QState* st = nullptr;
   QConst c = {};
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hs::EventPair ev;  // direct_quad_last_kernel_ms
   std::vector<void*> allocs;
 };
 
@@ -635,19 +636,14 @@ direct_status_t direct_quad_create(int32_t dtype, int32_t device, int32_t max_ba
   direct_quad_handle_t h = new direct_quad_handle_s();
   h->dtype = dtype; h->device = device; h->max_batch = max_batch; h->N = n_knots; h->rsz = dtype == DIRECT_F64 ? 8 : 4;
   const size_t B = max_batch, N = n_knots, r = h->rsz;
-  direct_status_t st = DIRECT_OK;
-  auto A = [&](void** pp, size_t bytes) {
-    if (st != DIRECT_OK) return;
-    hipError_t e = hipMalloc(pp, bytes ? bytes : 16);
-    if (e != hipSuccess) { st = qfail(DIRECT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e)); return; }
-    h->allocs.push_back(*pp);
-  };
-  A(&h->x0, B * NX * r); A(&h->xg, B * NX * r);
-  for (int i = 0; i < 2; i++) { A(&h->X[i], B * (N + 1) * NX * r); A(&h->U[i], B * N * NU * r); A(&h->Tg[i], B * N * 8 * sizeof(double)); }
-  A(&h->K, B * N * 48 * r); A(&h->kf, B * N * NU * r); A((void**)&h->st, B * sizeof(QState));
-  A(&h->o_cost, B * r); A((void**)&h->o_iters, B * 4); A(&h->o_x, B * (N + 1) * NX * r); A(&h->o_u, B * N * NU * r);
-  if (st == DIRECT_OK && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess))
-    st = qfail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
+  const size_t xb = B * (N + 1) * NX * r, ub = B * N * NU * r, tb = B * N * 8 * sizeof(double);
+  const hipError_t ae = hs::alloc_all(h->allocs, {
+      hs::want(&h->x0, B * NX * r), hs::want(&h->xg, B * NX * r),
+      hs::want(&h->X[0], xb), hs::want(&h->U[0], ub), hs::want(&h->Tg[0], tb), hs::want(&h->X[1], xb), hs::want(&h->U[1], ub), hs::want(&h->Tg[1], tb),
+      hs::want(&h->K, B * N * 48 * r), hs::want(&h->kf, ub), hs::want(&h->st, B * sizeof(QState)),
+      hs::want(&h->o_cost, B * r), hs::want(&h->o_iters, B * 4), hs::want(&h->o_x, xb), hs::want(&h->o_u, ub)});
+  direct_status_t st = ae == hipSuccess ? DIRECT_OK : qfail(DIRECT_ERR_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(ae));
+  if (st == DIRECT_OK && hs::create(h->ev) != hipSuccess) st = qfail(DIRECT_ERR_DEVICE, "hipEventCreate failed");
   if (st != DIRECT_OK) {
     direct_quad_destroy(h);
     return st;
@@ -661,8 +657,7 @@ direct_status_t direct_quad_destroy(direct_quad_handle_t h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
+  hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
 }
@@ -689,12 +684,11 @@ direct_status_t direct_quad_iterate(direct_quad_handle_t h, int32_t n_iters) {
   if (!h) return qfail(DIRECT_ERR_INVALID, "null handle");
   if (!h->begun) return qfail(DIRECT_ERR_INVALID, "direct_quad_begin has not been called");
   QHIP_TRY(hipSetDevice(h->device));
-  QHIP_TRY(hipEventRecord(h->ev0, h->stream));
+  QHIP_TRY(hs::start(h->ev, h->stream));
   if (h->dtype == DIRECT_F64) hipLaunchKernelGGL(k_quad_iterate<double>, dim3(h->B), dim3(64), 0, h->stream, make_q<double>(h), n_iters);
   else hipLaunchKernelGGL(k_quad_iterate<float>, dim3(h->B), dim3(64), 0, h->stream, make_q<float>(h), n_iters);
   QHIP_TRY(hipGetLastError());
-  QHIP_TRY(hipEventRecord(h->ev1, h->stream));
-  h->timed = true;
+  QHIP_TRY(hs::stop(h->ev, h->stream));
   return DIRECT_OK;
 }
 
@@ -757,10 +751,9 @@ direct_status_t direct_quad_set_stream(direct_quad_handle_t h, void* hip_stream)
 
 direct_status_t direct_quad_last_kernel_ms(direct_quad_handle_t h, double* ms) {
   if (!h || !ms) return qfail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->timed) return qfail(DIRECT_ERR_INVALID, "nothing has been timed yet");
-  QHIP_TRY(hipEventSynchronize(h->ev1));
+  if (!h->ev.timed) return qfail(DIRECT_ERR_INVALID, "nothing has been timed yet");
   float t = 0.f;
-  QHIP_TRY(hipEventElapsedTime(&t, h->ev0, h->ev1));
+  QHIP_TRY(hs::elapsed(h->ev, &t));
   *ms = (double)t;
   return DIRECT_OK;
 }
