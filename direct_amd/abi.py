@@ -127,6 +127,17 @@ AUDIT_OUTPUTS = ("t_total", "vpeak", "apeak", "jpeak", "vnorm", "anorm", "jnorm"
 AUDIT_VEL, AUDIT_ACC, AUDIT_JERK, AUDIT_CORRIDOR, AUDIT_INVALID = 1, 2, 4, 8, 256   # bits of `verdict` (0 = the plan passes)
 
 
+class PlanClearIn(C.Structure):  # direct_plan_clear_in_t (include/direct_cluster.h)
+    _fields_ = [("batch", C.c_int32), ("n_seg_max", C.c_int32), ("mem", C.c_int32), ("dtype", C.c_int32), ("n_seg", C.c_void_p),
+                ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p), ("map_lower", C.c_double * 3), ("resolution", C.c_double),
+                ("radius", C.c_double), ("depth", C.c_int32), ("reserved", C.c_int32), ("t_from", C.c_void_p)]
+
+
+class PlanClearOut(C.Structure):  # direct_plan_clear_out_t (include/direct_cluster.h)
+    _fields_ = [("status", C.c_void_p), ("clearance", C.c_void_p), ("where", C.c_void_p), ("t_min", C.c_void_p),
+                ("verdict", C.c_void_p), ("t_free", C.c_void_p), ("seg_clearance", C.c_void_p)]
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

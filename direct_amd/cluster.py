@@ -32,16 +32,21 @@ class PlanCheckOut(C.Structure):  # direct_plan_check_out_t
                 ("hit_box", C.c_void_p), ("seg_first", C.c_void_p), ("stats", C.c_void_p)]
 
 
+PlanClearIn, PlanClearOut = abi.PlanClearIn, abi.PlanClearOut  # direct_plan_clear_in_t, direct_plan_clear_out_t
+
+
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
            "direct_cluster_polygon_generation_batch", "direct_cluster_convex_test", "direct_cluster_last_ms",
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
-           "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch")
+           "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
+           "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
 MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
 PLAN_CHECK_INVALID = -1
+DIST_NONE = 0x7fffffff
 _BOUND = False
 
 
@@ -66,6 +71,9 @@ def _lib():
         L.direct_cluster_map_from_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.direct_cluster_get_map.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_plan_check_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_distance_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_get_distance_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_plan_clearance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -264,6 +272,72 @@ class ClusterGenerator:
         _check(_lib().direct_cluster_plan_check_batch(self.h, C.addressof(par), C.addressof(o)))
         if count:
             out.update(unresolved=int(stats[0]), box_tests=int(stats[1]))
+        return out
+
+    def build_distance_field(self, cap_vox=0):
+        """The exact squared Euclidean distance field of the map the handle holds now (direct_cluster_distance_field), in voxel
+        units, resident on the handle until the map changes.  cap_vox > 0 stores min(D2, cap_vox^2) and bounds the work per voxel
+        by cap_vox steps per axis.  -> dict(below_cap: voxels with a stored value below the cap, max_d2: the largest of them or -1)"""
+        stats = np.zeros(2, np.int64)
+        _check(_lib().direct_cluster_distance_field(self.h, int(cap_vox), stats.ctypes.data))
+        return dict(below_cap=int(stats[0]), max_d2=int(stats[1]))
+
+    def distance_field(self, out=None):
+        """The stored field as an int32 array of shape dims (direct_cluster_get_distance_field); DIST_NONE on an empty map.  out: an
+        int32 device tensor of shape dims to fetch into instead (returned)."""
+        if out is None:
+            d2 = np.zeros(self.dims, np.int32)
+            _check(_lib().direct_cluster_get_distance_field(self.h, abi.MEM_HOST, d2.ctypes.data))
+            return d2
+        import torch
+        assert out.is_cuda and out.dtype == torch.int32 and tuple(out.shape) == self.dims and out.is_contiguous()
+        torch.cuda.current_stream(out.device).synchronize()  # the handle's stream is not torch's
+        _check(_lib().direct_cluster_get_distance_field(self.h, abi.MEM_DEVICE, out.data_ptr()))
+        return out
+
+    def plan_clearance(self, n_seg, T, map_lower, resolution, bez=None, poly=None, depth=6, radius=0.0, t_from=None):
+        """A certified lower bound, in metres, on each solved plan's distance to the occupied voxels, from the resident distance field
+        (direct_cluster_plan_clearance_batch; build_distance_field must have run since the map last changed).  Inputs as check_plans;
+        radius >= 0: from when on the plan is closer than that.  NumPy arrays, or device tensors (then every output is one too).
+        -> dict(status, clearance, where [B][2], t_min, verdict, t_free, seg_clearance [B][N])"""
+        assert (bez is None) != (poly is None), "exactly one of bez and poly"
+        coef = bez if poly is None else poly
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        par = PlanClearIn(depth=int(depth), resolution=float(resolution), radius=float(radius), map_lower=(C.c_double * 3)(*lower))
+        if isinstance(T, np.ndarray) or not hasattr(T, "data_ptr"):
+            T = np.asarray(T)
+            real = np.float32 if T.dtype == np.float32 else np.float64
+            T, coef = np.ascontiguousarray(T, real), np.ascontiguousarray(coef, real)
+            n_seg = np.ascontiguousarray(n_seg, np.int32)
+            B, N = T.shape
+            tf = None if t_from is None else np.ascontiguousarray(t_from, np.float64)
+            out = dict(status=np.zeros(B, np.int32), clearance=np.zeros(B, np.float64), where=np.zeros((B, 2), np.int32),
+                       t_min=np.zeros(B, np.float64), verdict=np.zeros(B, np.int32), t_free=np.zeros(B, np.float64),
+                       seg_clearance=np.zeros((B, N), np.float64))
+            ptr = lambda a: a.ctypes.data
+            par.mem, par.dtype = abi.MEM_HOST, abi.F32 if real == np.float32 else abi.F64
+        else:
+            import torch
+            real = torch.float32 if T.dtype == torch.float32 else torch.float64
+            T, coef = T.to(real).contiguous(), coef.to(real).contiguous()
+            n_seg = n_seg.to(torch.int32).contiguous()
+            assert T.is_cuda and coef.is_cuda and n_seg.is_cuda
+            B, N = T.shape
+            tf = None if t_from is None else t_from.to(torch.float64).contiguous()
+            mk = lambda shape, dt, fill=0: torch.full(shape, fill, dtype=dt, device=T.device)
+            out = dict(status=mk((B,), torch.int32), clearance=mk((B,), torch.float64), where=mk((B, 2), torch.int32),
+                       t_min=mk((B,), torch.float64), verdict=mk((B,), torch.int32), t_free=mk((B,), torch.float64),
+                       seg_clearance=mk((B, N), torch.float64, float("nan")))
+            torch.cuda.current_stream(T.device).synchronize()  # the handle's stream is not torch's
+            ptr = lambda a: a.data_ptr()
+            par.mem, par.dtype = abi.MEM_DEVICE, abi.F32 if real == torch.float32 else abi.F64
+        assert tuple(coef.shape) == (B, N, 18) and tuple(n_seg.shape) == (B,) and (tf is None or tuple(tf.shape) == (B,))
+        par.batch, par.n_seg_max = B, N
+        par.n_seg, par.T = ptr(n_seg), ptr(T)
+        par.bez, par.poly = (ptr(coef), None) if poly is None else (None, ptr(coef))
+        par.t_from = None if tf is None else ptr(tf)
+        o = PlanClearOut(*[ptr(out[k]) for k in ("status", "clearance", "where", "t_min", "verdict", "t_free", "seg_clearance")])
+        _check(_lib().direct_cluster_plan_clearance_batch(self.h, C.addressof(par), C.addressof(o)))
         return out
 
     def set_stream(self, hip_stream):

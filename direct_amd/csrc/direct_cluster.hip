@@ -981,6 +981,8 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "grid_path.h"
 #include "map_cloud.h"
 #include "plan_check.h"
+#include "dist_field.h"
+#include "plan_clear.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1019,6 +1021,11 @@ struct direct_cluster_handle_s {
   unsigned long long* cloud_cnt = nullptr;  // [2] its counters
   hs::Block plan_ws;  // workspace of plan_check_batch (counters, start times, per-slot leaves, unresolved list), grown on demand
   hs::Block plan_io;  // device staging of its host arrays, grown on demand
+  int32_t* dist[2] = {nullptr, nullptr};  // the distance field (in dist[0]) and its ping-pong partner, allocated by the first distance_field
+  unsigned long long* dist_cnt = nullptr;  // [2] the counters behind its stats
+  bool dist_valid = false;  // dist[0] describes the map the handle holds
+  hs::Block clear_ws;  // workspace of plan_clearance_batch (start times, per-slot minima), grown on demand
+  hs::Block clear_io;  // device staging of its host arrays, grown on demand
 };
 
 namespace {
@@ -1101,7 +1108,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipSetDevice(h->cfg.device);
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
-  for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io}) hs::release(*b);
+  for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io}) hs::release(*b);
   hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
@@ -1109,6 +1116,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
 
 direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, const uint8_t* map_data) {
   if (!h || !map_data) return cfail(DIRECT_ERR_INVALID, "null argument");
+  h->dist_valid = false;  // the map is about to change: a distance field no longer describes it
   CHIP_TRY(hipSetDevice(h->cfg.device));
   CHIP_TRY(hipMemcpyAsync(h->map, map_data, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                           h->stream));
@@ -1122,6 +1130,7 @@ direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, c
 direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const direct_map_cloud_t* p, int64_t n_points, int32_t mem,
                                               const float* xyz, int64_t* stats) {
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+  h->dist_valid = false;  // whether or not the call succeeds: a distance field is rebuilt by its caller
   if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
   if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
   if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
@@ -1527,6 +1536,106 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_check_batch: ") + hipGetErrorString(e));
   if (out->stats) { out->stats[0] = (int64_t)(cnt[0] & 0xffffffffull); out->stats[1] = (int64_t)cnt[1]; }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t cap_vox, int64_t* stats) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (cap_vox < 0 || cap_vox > df::kMaxCap) return cfail(DIRECT_ERR_INVALID, "cap_vox outside [0, 1024]");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  if (!h->dist[0]) {  // all or nothing
+    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->dist[0], (size_t)D.G * sizeof(int32_t)), hs::want(&h->dist[1], (size_t)D.G * sizeof(int32_t)),
+                                                    hs::want(&h->dist_cnt, 2 * sizeof(unsigned long long))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: allocation: ") + hipGetErrorString(ae));
+  }
+  h->dist_valid = false;
+  DistDev A = {};
+  A.map = h->map; A.a = h->dist[0]; A.b = h->dist[1];
+  A.X = D.max_x; A.Y = D.max_y; A.Z = D.max_z; A.G = D.G; A.cap2 = df::cap2_of(cap_vox);
+  A.cnt = h->dist_cnt;
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(h->dist_cnt, 0, sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->dist_cnt + 1, 0xff, sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = dist_field_launch(A, stats != nullptr, h->stream);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  unsigned long long cnt[2] = {0, 0};
+  if (e == hipSuccess && stats) e = hipMemcpyAsync(cnt, h->dist_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: ") + hipGetErrorString(e));
+  h->dist_valid = true;
+  if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)(int32_t)(cnt[1] & 0xffffffffull); }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_distance_field(direct_cluster_handle_t h, int32_t mem, int32_t* d2) {
+  if (!h || !d2) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  CHIP_TRY(hipMemcpyAsync(d2, h->dist[0], (size_t)h->D.G * sizeof(int32_t), mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                          h->stream));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, const direct_plan_clear_in_t* in, direct_plan_clear_out_t* out) {
+  if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->n_seg_max <= 0) return cfail(DIRECT_ERR_INVALID, "batch and n_seg_max must be positive");
+  if ((in->bez != nullptr) == (in->poly != nullptr)) return cfail(DIRECT_ERR_INVALID, "exactly one of bez and poly");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "dtype is neither DIRECT_F32 nor DIRECT_F64");
+  if (in->depth < 0 || in->depth > pk::kMaxDepth) return cfail(DIRECT_ERR_INVALID, "depth outside [0, 12]");
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  if (!std::isfinite(in->radius) || !(in->radius >= 0.0)) return cfail(DIRECT_ERR_INVALID, "radius must be finite and not negative");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
+  const size_t B = (size_t)in->batch, nm = (size_t)in->n_seg_max, slots = B * nm;
+  if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  const size_t r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  // workspace: S, then per slot the minimum, its leaf, the first leaf below the radius
+  const size_t w_min = up(B * (nm + 1) * sizeof(double)), w_leaf = w_min + up(slots * sizeof(double)), w_below = w_leaf + up(slots * sizeof(int)),
+               w_total = w_below + up(slots * sizeof(int));
+  CHIP_TRY(hs::grow(h->clear_ws, h->stream, w_total));
+  char* W = (char*)h->clear_ws.p;
+  ClearDev A = {};
+  for (int a = 0; a < 3; a++) A.G.lower[a] = in->map_lower[a];
+  A.G.inv = 1.0 / in->resolution;
+  A.G.resolution = in->resolution;
+  A.G.size[0] = D.max_x; A.G.size[1] = D.max_y; A.G.size[2] = D.max_z;
+  A.batch = in->batch; A.nmax = in->n_seg_max; A.depth = in->depth; A.poly = in->poly != nullptr; A.has_from = in->t_from != nullptr;
+  A.radius = in->radius;
+  A.field = h->dist[0]; A.YZ = D.max_yz; A.Z = D.max_z;
+  A.S = (double*)W; A.ws_min = (double*)(W + w_min); A.ws_leaf = (int*)(W + w_leaf); A.ws_below = (int*)(W + w_below);
+  // host arrays go through one staging block of the call's own; seg_clearance alone is filled (0xff: entries past n_seg read NaN)
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &A.T, in->T, slots * r);
+  hs::stage_in(st, &A.coef, in->poly ? in->poly : in->bez, slots * 18 * r);
+  hs::stage_in(st, &A.t_from, in->t_from, B * 8);
+  hs::stage_out(st, &A.status, out->status, B * 4);
+  hs::stage_out(st, &A.clearance, out->clearance, B * 8);
+  hs::stage_out(st, &A.where, out->where, B * 8);
+  hs::stage_out(st, &A.t_min, out->t_min, B * 8);
+  hs::stage_out(st, &A.verdict, out->verdict, B * 4);
+  hs::stage_out(st, &A.t_free, out->t_free, B * 8);
+  hs::stage_out(st, &A.seg_clearance, out->seg_clearance, slots * 8, 0xff);
+  CHIP_TRY(hs::stage_upload(st, h->clear_io, h->stream));
+  PlanDev P = {};  // what k_plan_starts reads
+  P.batch = A.batch; P.nmax = A.nmax; P.has_from = A.has_from; P.n_seg = A.n_seg; P.T = A.T; P.t_from = A.t_from; P.S = (double*)W;
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = in->dtype == DIRECT_F32 ? plan_clear_launch<float>(P, A, h->stream) : plan_clear_launch<double>(P, A, h->stream);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(st, h->stream, e);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_clearance_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 

@@ -107,6 +107,49 @@ class polyhedronGenerator {
     return c;
   }
 
+  // The exact squared Euclidean distance field of the map the generator holds NOW (direct_cluster_distance_field), resident
+  // until the map changes: call it after every map update and before trajectoryClearance.  cap_vox > 0 stores min(D2, cap_vox^2).
+  // -> the number of voxels with a stored value below the cap
+  long long buildDistanceField(int cap_vox = 0) {
+    int64_t stats[2] = {0, -1};
+    if (direct_cluster_distance_field(h_, cap_vox, stats) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return (long long)stats[0];
+  }
+
+  // One plan's certified distance to the occupied voxels (direct_cluster_plan_clearance_batch), arguments as checkTrajectory's.
+  // A lower bound from the distance field and the bounding boxes of pieces of duration T_i / 2^depth: a negative value certifies
+  // nothing.  radius: the vehicle's, on a map that is NOT inflated.  t_from < 0 judges the whole plan.
+  struct PlanClearance {
+    int verdict = DIRECT_PLAN_CHECK_INVALID;   // 0: every judged piece keeps `radius`; 1: not
+    double clearance = 0;                      // metres, the minimum over the judged pieces (+inf on an empty map)
+    double t_min = 0;                          // start time of the piece that attains it
+    double t_free = 0;                         // certified to keep `radius` before this time (t_total when the verdict is 0)
+    int segment = -1, leaf = -1;               // the piece that attains the minimum
+    bool clear() const { return verdict == 0; }
+  };
+  template <class Mat, class Vec>
+  PlanClearance trajectoryClearance(const Mat& polyCoeff, const Vec& time, int depth = 6, double radius = 0.0, double t_from = -1.0) {
+    const int N = (int)time.size();
+    std::vector<double> poly((size_t)N * 18), T(N);
+    for (int k = 0; k < N; k++) {
+      T[k] = time(k);
+      for (int q = 0; q < 18; q++) poly[(size_t)k * 18 + q] = polyCoeff(k, q);
+    }
+    int32_t n_seg = N, status = 0, verdict = 0, where[2] = {-1, -1};
+    PlanClearance c;
+    direct_plan_clear_in_t in{};
+    in.batch = 1; in.n_seg_max = N; in.mem = DIRECT_MEM_HOST; in.dtype = DIRECT_F64;
+    in.n_seg = &n_seg; in.T = T.data(); in.poly = poly.data();
+    for (int a = 0; a < 3; a++) in.map_lower[a] = lower_[a];
+    in.resolution = res_; in.radius = radius; in.depth = depth;
+    in.t_from = t_from < 0.0 ? nullptr : &t_from;
+    direct_plan_clear_out_t out{};
+    out.status = &status; out.verdict = &verdict; out.clearance = &c.clearance; out.t_min = &c.t_min; out.t_free = &c.t_free; out.where = where;
+    if (direct_cluster_plan_clearance_batch(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    c.verdict = verdict; c.segment = where[0]; c.leaf = where[1];
+    return c;
+  }
+
   std::array<int, 3> coord2Index(const std::array<double, 3>& c) const {  // :10-18
     auto f = [&](double v, double lo, int mx) {
       int i = (int)((v - lo) * inv_res_);

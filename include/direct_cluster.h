@@ -294,11 +294,114 @@ typedef struct {
 direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in,
                                                 direct_plan_check_out_t* out);
 
+/* ---- distance field of the resident map (no reference counterpart) --------------------------------------------------
+ * The exact squared Euclidean distance field of the map the handle holds NOW.  For every voxel v of the map,
+ *   D2[v] = min over voxels u with byte 1 of (vx-ux)^2 + (vy-uy)^2 + (vz-uz)^2,
+ * an int32 in voxel units with the map's own layout (x * max_y * max_z + y * max_z + z).  An occupied voxel has D2 = 0; a map
+ * with no occupied voxel has D2 = +infinity everywhere; outside the map there is nothing, so no border convention enters.  The
+ * STORED value is min(D2, cap2), cap2 = cap_vox * cap_vox for cap_vox > 0 and DIRECT_DIST_NONE for cap_vox == 0: a stored cap2
+ * means "at least this far".  With cap_vox == 0 the field is exact everywhere and DIRECT_DIST_NONE appears only on an empty map.
+ * Dimensions are at most 1024 per axis, so every finite D2 is below 2^22 and no sum overflows; an infinite source is skipped,
+ * never added to.  All integer work: the result is a pure function of the map, whatever the launch shape.
+ * The field is resident on the handle (two buffers of 4 B per voxel, allocated by the first call, freed in
+ * direct_cluster_destroy) and VALID from a successful build until the next direct_cluster_set_map or
+ * direct_cluster_map_from_cloud call, which mark it stale whether or not they succeed.  direct_cluster_get_distance_field and
+ * direct_cluster_plan_clearance_batch return DIRECT_ERR_INVALID with nothing launched when the field is absent or stale: they
+ * never rebuild silently, the caller decides when to pay for a rebuild.
+ * stats (HOST, [2], or NULL): [0] the number of voxels with a stored value below cap2, [1] the largest stored value below cap2,
+ * or -1 if there is none.  Asking for it adds one atomic add and one atomic max per wave of the last pass, on counters of their
+ * own.
+ * DIRECT_ERR_INVALID, nothing launched: a NULL handle; cap_vox < 0 or above 1024; an unknown mem; a NULL d2; a handle without a
+ * map.  Both calls run on the handle's stream and synchronise before they return; the build runs between the handle's event
+ * pair, so direct_cluster_last_ms covers it.  They leave resident clusters, the path workspace and the plan-check workspace
+ * alone. */
+#define DIRECT_DIST_NONE 0x7fffffff
+direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t cap_vox, int64_t* stats /* HOST [2] or NULL */);
+/* The stored field, d2[max_x][max_y][max_z] int32 in memory kind `mem` */
+direct_status_t direct_cluster_get_distance_field(direct_cluster_handle_t h, int32_t mem, int32_t* d2);
+
+/* ---- metric clearance of plans (no reference counterpart) --------------------------------------------------------------
+ * For each solved plan a certified lower bound on its distance to the occupied voxels, in metres, from the resident distance
+ * field; where and when that bound is attained; and from when on the plan is closer than `radius`.  One map then serves any
+ * vehicle radius, and candidate plans can be ranked by the air around them.
+ * The inputs are those of direct_plan_check_in_t minus margin and outside_blocks, plus radius (finite, >= 0 metres; 0: only the
+ * bound is wanted).  Rows and their validity, control points (item 1 of the plan-check block), leaves and their time spans
+ * (item 2), "a leaf is judged iff its end time is > t_from[b]" (item 4) and the invalid rows of item 6 are EXACTLY the plan
+ * check's.  All arithmetic is double with contraction off, written with plain *, +, - and sqrt.  inv = 1.0 / resolution is
+ * computed once on the host.  For one leaf with six points L_j, per axis a:
+ *   lo_a = min_j L_j[a], hi_a = max_j L_j[a], c_a = (lo_a + hi_a) * 0.5, e_a = (hi_a - lo_a) * 0.5
+ *   half = sqrt((e_0*e_0 + e_1*e_1) + e_2*e_2)
+ *   q_a = (c_a - map_lower[a]) * inv; i_a = size_a - 1 when q_a >= size_a, 0 when !(q_a >= 1), else (int)q_a - compared
+ *         before it is converted
+ *   m_a = ((double)i_a + 0.5) * resolution + map_lower[a], r_a = c_a - m_a
+ *   off = sqrt((r_0*r_0 + r_1*r_1) + r_2*r_2)
+ * and with d2 the stored field value at (i_0, i_1, i_2):
+ *   bound = +inf when d2 == DIRECT_DIST_NONE, else ((sqrt((double)d2) - K) * resolution - off) - half,
+ * K = 0x1.bb67ae8584cabp-1 (0.8660254037844387), the smallest double not below sqrt(3)/2.
+ * WHY IT IS A LOWER BOUND: the nearest occupied voxel CENTRE is resolution * sqrt(d2) from the voxel centre m; an occupied cube
+ * reaches at most sqrt(3)/2 * resolution from its centre; the distance to a set is 1-Lipschitz, c is `off` from m, and every
+ * point of the leaf's piece of curve lies in the box of its control points, hence within `half` of c.  A box centre outside the
+ * map goes through the same formula with the clamped voxel, `off` carrying the displacement.  A capped field only lowers d2, so
+ * the bound stays valid (and cannot exceed about cap_vox * resolution).  Unlike the plan check's verdict this is NOT an exact
+ * predicate: it is certified up to the rounding of the fifteen-odd double operations above, about 1e-15 relative.  A negative
+ * bound is reported as computed and means "nothing certified".  A larger depth shrinks `half`.
+ * Outputs (any but status may be NULL):
+ *   status [batch]                 0 or -1 (required)
+ *   clearance [batch] (double)     the minimum bound over the judged leaves, in metres; +inf when no leaf is judged or every
+ *                                  bound is +inf
+ *   where [batch][2]               segment and leaf of that minimum, the first in (segment, leaf) order among equal values;
+ *                                  (-1, -1) when there is none (the clearance is +inf)
+ *   t_min [batch] (double)         that leaf's start time; S_n when there is none
+ *   verdict [batch]                0: every judged bound is >= radius; 1: not; DIRECT_PLAN_CHECK_INVALID for an invalid row
+ *   t_free [batch] (double)        the start time of the first judged leaf with bound < radius, in (segment, leaf) order; S_n
+ *                                  when the verdict is 0
+ *   seg_clearance [batch][n_seg_max] (double)  the minimum per segment (+inf for a segment without a judged leaf).  Entries past
+ *                                  n_seg are untouched in device memory and all-ones bytes (a NaN) in host memory.
+ * Invalid rows: status = -1, verdict = DIRECT_PLAN_CHECK_INVALID, clearance NaN, t_min = t_free = 0, -1 in where, NaN in the
+ * first min(n_seg, n_seg_max) entries of seg_clearance; other rows are unaffected.  The result is that of evaluating all 2^D
+ * leaves of every segment one by one; minima are taken with a commutative, associative merge, so it does not depend on the
+ * launch shape.
+ * DIRECT_ERR_INVALID, nothing launched: as direct_cluster_plan_check_batch (a NULL handle / struct / n_seg / T / status; a
+ * non-positive batch / n_seg_max; not exactly one of bez and poly; an unknown mem or dtype; depth outside [0, 12]; a non-finite
+ * map_lower; resolution <= 0 or not finite; a handle without a map), plus a radius < 0 or not finite, and a handle without a
+ * valid distance field.  DIRECT_ERR_UNSUPPORTED: batch * n_seg_max of 2^31 or more.  Runs on the handle's stream and
+ * synchronises before it returns; direct_cluster_last_ms covers its kernels (not the copies of host arrays).  Its workspace
+ * (8 B per row and 24 B per segment slot) and the staging of host arrays are blocks of its own on the handle, grown on demand
+ * and freed in direct_cluster_destroy.  It leaves resident clusters, the path workspace and the plan-check workspace alone. */
+typedef struct {
+  int32_t batch, n_seg_max;
+  int32_t mem;               /* direct_mem_t: where every array of `in` and `out` lives */
+  int32_t dtype;             /* direct_dtype_t: storage type of T, bez, poly */
+  const int32_t* n_seg;      /* [batch] */
+  const void* T;             /* [batch][n_seg_max] */
+  const void* bez;           /* [batch][n_seg_max][18] or NULL } exactly one */
+  const void* poly;          /* [batch][n_seg_max][18] or NULL }            */
+  double map_lower[3];
+  double resolution;
+  double radius;             /* >= 0 metres; 0: only the bound is wanted */
+  int32_t depth;             /* D in [0, 12] */
+  int32_t reserved;
+  const double* t_from;      /* [batch] or NULL */
+} direct_plan_clear_in_t;
+
+typedef struct {
+  int32_t* status;           /* [batch], required */
+  double* clearance;         /* [batch] or NULL */
+  int32_t* where;            /* [batch][2] or NULL */
+  double* t_min;             /* [batch] or NULL */
+  int32_t* verdict;          /* [batch] or NULL */
+  double* t_free;            /* [batch] or NULL */
+  double* seg_clearance;     /* [batch][n_seg_max] or NULL */
+} direct_plan_clear_out_t;
+
+direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, const direct_plan_clear_in_t* in,
+                                                    direct_plan_clear_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
- * grid_path_batch / map_from_cloud / plan_check_batch call */
+ * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
