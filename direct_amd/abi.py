@@ -138,6 +138,20 @@ class PlanClearOut(C.Structure):  # direct_plan_clear_out_t (include/direct_clus
                 ("verdict", C.c_void_p), ("t_free", C.c_void_p), ("seg_clearance", C.c_void_p)]
 
 
+class CubeCorridorIn(C.Structure):  # direct_cube_corridor_in_t (include/direct_cluster.h)
+    _fields_ = [("batch", C.c_int32), ("path_capacity", C.c_int32), ("mem_in", C.c_int32), ("itr_inflate_max", C.c_int32),
+                ("path_xyz", C.c_void_p), ("path_len", C.c_void_p), ("pop_back", C.c_int32), ("seg_capacity", C.c_int32),
+                ("p_max", C.c_int32), ("plane_dtype", C.c_int32), ("resolution", C.c_double), ("map_lower", C.c_double * 3)]
+
+
+class CubeCorridorOut(C.Structure):  # direct_cube_corridor_out_t (include/direct_cluster.h)
+    _fields_ = [("mem", C.c_int32), ("reserved", C.c_int32), ("n_seg", C.c_void_p), ("n_planes", C.c_void_p), ("planes", C.c_void_p),
+                ("seeds", C.c_void_p), ("centers", C.c_void_p), ("cube_idx", C.c_void_p), ("rtn", C.c_void_p)]
+
+
+CUBE_CORRIDOR_OUTPUTS = ("n_seg", "n_planes", "planes", "seeds", "centers", "cube_idx", "rtn")   # the arrays of CubeCorridorOut
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

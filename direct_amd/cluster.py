@@ -33,13 +33,15 @@ class PlanCheckOut(C.Structure):  # direct_plan_check_out_t
 
 
 PlanClearIn, PlanClearOut = abi.PlanClearIn, abi.PlanClearOut  # direct_plan_clear_in_t, direct_plan_clear_out_t
+CubeCorridorIn, CubeCorridorOut = abi.CubeCorridorIn, abi.CubeCorridorOut  # direct_cube_corridor_in_t, direct_cube_corridor_out_t
 
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
            "direct_cluster_polygon_generation_batch", "direct_cluster_convex_test", "direct_cluster_last_ms",
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
            "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
-           "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch")
+           "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
+           "direct_cluster_cube_corridor_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -47,6 +49,7 @@ MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
 PLAN_CHECK_INVALID = -1
 DIST_NONE = 0x7fffffff
+CUBE_CORRIDOR_OK, CUBE_CORRIDOR_OVERFLOW, CUBE_CORRIDOR_BAD_PATH = 0, 1, 2
 _BOUND = False
 
 
@@ -74,6 +77,7 @@ def _lib():
         L.direct_cluster_distance_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_get_distance_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_plan_clearance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_cube_corridor_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -86,6 +90,7 @@ def _check(st):
 class ClusterGenerator:
     def __init__(self, dims, max_batch=64, cluster_capacity=50000, candidate_capacity=10000, device=0):
         self.dims = tuple(int(d) for d in dims)
+        self.device = int(device)
         self.max_batch, self.ccap, self.kcap = int(max_batch), int(cluster_capacity), int(candidate_capacity)
         cfg = Config(device, self.dims[0], self.dims[1], self.dims[2], self.max_batch, self.ccap, self.kcap, 0)
         h = C.c_void_p()
@@ -204,15 +209,28 @@ class ClusterGenerator:
         return dict(planes=cut(pl, npl, plane_capacity), plane_int=cut(pi, npl, plane_capacity),
                     vertices=cut(vt, nv, vertex_capacity), center=ctr, degenerate=deg, n_planes=npl, n_vertices=nv, rtn=rtn)
 
-    def grid_paths(self, starts, goals, path_capacity=4096, max_rounds=0, want_dist=False):
+    def grid_paths(self, starts, goals, path_capacity=4096, max_rounds=0, want_dist=False, mem="host"):
         """Optimal 26-connected voxel paths on the handle's map for a batch of (start, goal) voxel-index pairs
         (direct_cluster_grid_path_batch; stands where the reference calls gridPathFinder::AstarSearch).  -> dict(paths: list
         of [n][3] int32 arrays, start first (the first path_capacity voxels on GRID_PATH_OVERFLOW, empty without a path),
-        path_len, path_cost, rtn, stats [B][2] (rounds, tile visits), dist [B][X*Y*Z] float64 or None)"""
+        path_len, path_cost, rtn, stats [B][2] (rounds, tile visits), dist [B][X*Y*Z] float64 or None).
+        mem="device": the outputs stay on the device, as tensors in the C-ABI's own layout, for cube_corridors to read in place
+        -> dict(path_xyz [B][path_capacity][3] int32, path_len, path_cost, rtn, stats)"""
         starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
         goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
-        assert starts.shape == goals.shape
+        assert starts.shape == goals.shape and mem in ("host", "device")
         B, cap = starts.shape[0], int(path_capacity)
+        if mem == "device":
+            import torch
+            assert not want_dist
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
+            out = dict(path_xyz=z((B, cap, 3), torch.int32), path_len=z(B, torch.int32), path_cost=z(B, torch.float64),
+                       stats=z((B, 2), torch.int32), rtn=z(B, torch.int32))
+            torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
+            _check(_lib().direct_cluster_grid_path_batch(self.h, B, starts.ctypes.data, goals.ctypes.data, cap, int(max_rounds),
+                                                         abi.MEM_DEVICE, out["path_xyz"].data_ptr(), out["path_len"].data_ptr(),
+                                                         out["path_cost"].data_ptr(), None, out["stats"].data_ptr(), out["rtn"].data_ptr()))
+            return out
         xyz = np.zeros((B, cap, 3), np.int32)
         n, rtn, stats = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2), np.int32)
         cost = np.zeros(B, np.float64)
@@ -338,6 +356,47 @@ class ClusterGenerator:
         par.t_from = None if tf is None else ptr(tf)
         o = PlanClearOut(*[ptr(out[k]) for k in ("status", "clearance", "where", "t_min", "verdict", "t_free", "seg_clearance")])
         _check(_lib().direct_cluster_plan_clearance_batch(self.h, C.addressof(par), C.addressof(o)))
+        return out
+
+    def cube_corridors(self, paths, path_len, map_lower, resolution, itr_inflate_max=1000, pop_back=True, seg_capacity=64, p_max=6,
+                       dtype=np.float64):
+        """The corridors of a batch of grid paths in the reference's is_cluster_on == false mode, every polytope the inflated cube
+        of its seed voxel (direct_cluster_cube_corridor_batch): one call for all rows, planes in the optimiser's input layout.
+        paths [B][path_capacity][3] int32 and path_len [B]: the outputs of the grid-path call, as NumPy arrays or as device tensors
+        (grid_paths(mem="device")); every output is then of the same kind.  pop_back: corridorGeneration's walk (True) or
+        corridorInsertGeneration's from an empty corridor (False).  dtype: float64, or float32 as one rounding of it.
+        -> dict(n_seg [B], n_planes [B][S], planes [B][S][p_max][4], seeds [B][S][3], centers [B][S][3], cube_idx [B][S][6], rtn [B]),
+        S = seg_capacity; entries from a row's n_seg on are zero"""
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        f32 = np.dtype(dtype) == np.float32
+        par = CubeCorridorIn(itr_inflate_max=int(itr_inflate_max), pop_back=int(bool(pop_back)), seg_capacity=int(seg_capacity),
+                             p_max=int(p_max), plane_dtype=abi.F32 if f32 else abi.F64, resolution=float(resolution),
+                             map_lower=(C.c_double * 3)(*lower))
+        S, P = int(seg_capacity), int(p_max)
+        if isinstance(paths, np.ndarray) or not hasattr(paths, "data_ptr"):
+            paths, path_len = np.ascontiguousarray(paths, np.int32), np.ascontiguousarray(path_len, np.int32)
+            B = paths.shape[0]
+            real = np.float32 if f32 else np.float64
+            z = lambda shape, dt: np.zeros(shape, dt)
+            ptr = lambda a: a.ctypes.data
+            par.mem_in = mem = abi.MEM_HOST
+        else:
+            import torch
+            paths, path_len = paths.to(torch.int32).contiguous(), path_len.to(torch.int32).contiguous()
+            assert paths.is_cuda and path_len.is_cuda
+            B = paths.shape[0]
+            real = torch.float32 if f32 else torch.float64
+            z = lambda shape, dt: torch.zeros(shape, dtype={np.int32: torch.int32}.get(dt, dt), device=paths.device)
+            torch.cuda.current_stream(paths.device).synchronize()  # the handle's stream is not torch's
+            ptr = lambda a: a.data_ptr()
+            par.mem_in = mem = abi.MEM_DEVICE
+        assert paths.ndim == 3 and paths.shape[2] == 3 and tuple(path_len.shape) == (B,)
+        par.batch, par.path_capacity = B, int(paths.shape[1])
+        par.path_xyz, par.path_len = ptr(paths), ptr(path_len)
+        out = dict(n_seg=z(B, np.int32), n_planes=z((B, S), np.int32), planes=z((B, S, P, 4), real), seeds=z((B, S, 3), real),
+                   centers=z((B, S, 3), real), cube_idx=z((B, S, 6), np.int32), rtn=z(B, np.int32))
+        o = CubeCorridorOut(mem, 0, *[ptr(out[k]) for k in abi.CUBE_CORRIDOR_OUTPUTS])
+        _check(_lib().direct_cluster_cube_corridor_batch(self.h, C.addressof(par), C.addressof(o)))
         return out
 
     def set_stream(self, hip_stream):

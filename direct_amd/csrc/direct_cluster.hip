@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/direct_cluster.h"
+#include "cube_corridor_math.h"
 #include "grid_path_math.h"
 #include "host_stage.h"
 #include "hull_core.h"
@@ -983,6 +984,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "plan_check.h"
 #include "dist_field.h"
 #include "plan_clear.h"
+#include "cube_corridor.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1026,6 +1028,8 @@ struct direct_cluster_handle_s {
   bool dist_valid = false;  // dist[0] describes the map the handle holds
   hs::Block clear_ws;  // workspace of plan_clearance_batch (start times, per-slot minima), grown on demand
   hs::Block clear_io;  // device staging of its host arrays, grown on demand
+  hs::Block cube_ws;   // workspace of cube_corridor_batch (the cube of every path slot, the walks' stacks), grown on demand
+  hs::Block cube_in, cube_out;  // device staging of its host inputs / host outputs (two memory kinds: two blocks), grown on demand
 };
 
 namespace {
@@ -1108,7 +1112,9 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipSetDevice(h->cfg.device);
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
-  for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io}) hs::release(*b);
+  for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
+                       &h->cube_out})
+    hs::release(*b);
   hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
@@ -1636,6 +1642,57 @@ direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, c
   e = hs::stage_download(st, h->stream, e);
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_clearance_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out) {
+  if (!h || !in || !out || !in->path_xyz || !in->path_len) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->path_capacity <= 0 || in->seg_capacity <= 0 || in->itr_inflate_max <= 0)
+    return cfail(DIRECT_ERR_INVALID, "batch, path_capacity, seg_capacity and itr_inflate_max must be positive");
+  if (in->p_max < cc::kPlanes) return cfail(DIRECT_ERR_INVALID, "p_max below 6");
+  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
+    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->plane_dtype != DIRECT_F32 && in->plane_dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "plane_dtype is neither DIRECT_F32 nor DIRECT_F64");
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
+  if (slots >= (1ull << 28) || segs * (size_t)in->p_max >= (1ull << 28))
+    return cfail(DIRECT_ERR_UNSUPPORTED, "batch * path_capacity or batch * seg_capacity * p_max of 2^28 or more");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  const size_t w_stack = (slots * 6 * sizeof(int) + 255) & ~(size_t)255;
+  CHIP_TRY(hs::grow(h->cube_ws, h->stream, w_stack + slots * sizeof(int)));
+  CubeDev A = {};
+  A.batch = in->batch; A.path_cap = in->path_capacity; A.seg_cap = in->seg_capacity; A.p_max = in->p_max;
+  A.itr_inflate_max = in->itr_inflate_max; A.pop_back = in->pop_back ? 1 : 0;
+  A.res = in->resolution;
+  for (int a = 0; a < 3; a++) A.lower[a] = in->map_lower[a];
+  A.cube = (int*)h->cube_ws.p;
+  A.stack = (int*)((char*)h->cube_ws.p + w_stack);
+  const size_t r = in->plane_dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(out->mem == DIRECT_MEM_HOST);
+  hs::stage_in(si, &A.path_xyz, in->path_xyz, slots * 3 * sizeof(int32_t));
+  hs::stage_in(si, &A.path_len, in->path_len, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_seg, out->n_seg, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_planes, out->n_planes, segs * sizeof(int32_t));
+  hs::stage_out(so, &A.planes, out->planes, segs * (size_t)in->p_max * 4 * r);
+  hs::stage_out(so, &A.seeds, out->seeds, segs * 3 * r);
+  hs::stage_out(so, &A.centers, out->centers, segs * 3 * r);
+  hs::stage_out(so, &A.cube_idx, out->cube_idx, segs * 6 * sizeof(int32_t));
+  hs::stage_out(so, &A.rtn, out->rtn, B * sizeof(int32_t));
+  CHIP_TRY(hs::stage_upload(si, h->cube_in, h->stream));
+  CHIP_TRY(hs::stage_upload(so, h->cube_out, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  const int blocks = (int)std::min<size_t>((slots + 63) / 64, 8192);  // a fixed grid beyond 524288 slots: the lanes stride
+  hipLaunchKernelGGL(k_cube_inflate, dim3(blocks), dim3(64), 0, h->stream, D, A);
+  if (in->plane_dtype == DIRECT_F32) hipLaunchKernelGGL(k_cube_walk<float>, dim3(in->batch), dim3(64), 0, h->stream, A);
+  else hipLaunchKernelGGL(k_cube_walk<double>, dim3(in->batch), dim3(64), 0, h->stream, A);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("cube_corridor_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 

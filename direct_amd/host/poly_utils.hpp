@@ -15,6 +15,8 @@
 //     unfinished walk is waiting for and runs them as one batch - the form the device wants.  A walk's result does not
 //     depend on the other walks (getConvexPoly is a function of the seed voxel and the map), so both give the same
 //     corridors.
+//   * cubeCorridorBatch(gridPaths, corridors, pop_back) the corridors of is_cluster_on == false (every polytope the inflated
+//     cube of its seed voxel) for many paths in ONE device call, direct_cluster_cube_corridor_batch: no rounds at all
 // Corridor / Polytope types are template parameters read through the member names of
 // global_planner/include/global_planner/utils/data_type.h:124-245 (polyhedrons, planes, center, seed_coord,
 // appendPlane, setSeed / setCenter where they exist); direct::PlainCorridor of ddp_optimizer.hpp fits.
@@ -220,6 +222,66 @@ class polyhedronGenerator {
                                             const std::vector<Corridor*>& corridors) {
     if (!has_map_) throw std::runtime_error("polyhedronGenerator: no map");
     return walk(gridPaths, corridors, true);
+  }
+
+  // The corridors of is_cluster_on == false - paramSet's (itr_inflate_max, itr_cluster_max) = (1000, 0), every polytope the
+  // inflated cube of its seed voxel - for many paths in ONE device call (direct_cluster_cube_corridor_batch) instead of one
+  // round trip per polytope of the longest corridor: coordinates go through coord2Index, the call walks every path from an empty
+  // corridor, and corridors[p] is filled as walk() fills it (planes, center, seed_coord).  pop_back: corridorGeneration's walk
+  // (true) or corridorInsertGeneration's (false).  Returns, per path, whether its corridor was generated; a path that is
+  // empty is left without polytopes and reported false.  The generator's itr_cluster_max plays no part.
+  template <class Corridor>
+  std::vector<bool> cubeCorridorBatch(const std::vector<std::vector<std::array<double, 3>>>& gridPaths,
+                                      const std::vector<Corridor*>& corridors, bool pop_back = true) {
+    if (!has_map_) throw std::runtime_error("polyhedronGenerator: no map");
+    const size_t np = gridPaths.size();
+    std::vector<bool> ok(np, false);
+    if (np == 0) return ok;
+    size_t cap = 1;
+    for (const auto& p : gridPaths) cap = std::max(cap, p.size());
+    std::vector<int32_t> xyz(np * cap * 3, 0), len(np);
+    for (size_t p = 0; p < np; p++) {
+      len[p] = (int32_t)gridPaths[p].size();
+      for (size_t i = 0; i < gridPaths[p].size(); i++) {
+        const std::array<int, 3> idx = coord2Index(gridPaths[p][i]);
+        for (int a = 0; a < 3; a++) xyz[(p * cap + i) * 3 + a] = idx[a];
+      }
+    }
+    direct_cube_corridor_in_t in{};
+    in.batch = (int32_t)np; in.path_capacity = (int32_t)cap; in.mem_in = DIRECT_MEM_HOST; in.itr_inflate_max = itr_inflate_;
+    in.path_xyz = xyz.data(); in.path_len = len.data(); in.pop_back = pop_back ? 1 : 0;
+    in.seg_capacity = (int32_t)cap;  // a corridor has at most one polytope per path point: no row can overflow
+    in.p_max = 6; in.plane_dtype = DIRECT_F64; in.resolution = res_;
+    for (int a = 0; a < 3; a++) in.map_lower[a] = lower_[a];
+    const size_t segs = np * cap;
+    std::vector<int32_t> n_seg(np), rtn(np);
+    std::vector<double> planes(segs * 24), seeds(segs * 3), centers(segs * 3);
+    direct_cube_corridor_out_t out{};
+    out.mem = DIRECT_MEM_HOST; out.n_seg = n_seg.data(); out.planes = planes.data(); out.seeds = seeds.data();
+    out.centers = centers.data(); out.rtn = rtn.data();
+    if (direct_cluster_cube_corridor_batch(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    rounds_ = 1;
+    polytopes_ = 0;
+    for (size_t p = 0; p < np; p++) {
+      if (rtn[p] != DIRECT_CUBE_CORRIDOR_OK) continue;
+      ok[p] = true;
+      Corridor& cor = *corridors[p];
+      for (int k = 0; k < n_seg[p]; k++) {
+        const size_t at = p * cap + (size_t)k;
+        typename std::decay<decltype(cor.polyhedrons[0])>::type pt{};
+        for (int j = 0; j < 6; j++) {
+          const double* pl = &planes[(at * 6 + j) * 4];
+          pt.appendPlane({pl[0], pl[1], pl[2], pl[3]});
+        }
+        for (int a = 0; a < 3; a++) {
+          set_elem(pt.center, a, centers[at * 3 + a]);
+          set_elem(pt.seed_coord, a, seeds[at * 3 + a]);
+        }
+        cor.polyhedrons.push_back(pt);
+        polytopes_++;
+      }
+    }
+    return ok;
   }
 
  private:

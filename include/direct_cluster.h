@@ -397,11 +397,89 @@ typedef struct {
 direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, const direct_plan_clear_in_t* in,
                                                     direct_plan_clear_out_t* out);
 
+/* ---- cube corridors: the corridors of a batch of grid paths in one call (grid path -> corridor -> optimiser) ------------
+ * The corridor of the reference with is_cluster_on == false: paramSet then sets (itr_inflate_max, itr_cluster_max) = (1000, 0)
+ * (cluster_server_cpu.cpp:91-97) and every polytope is the inflated cube of its seed voxel alone, six planes - a pure function
+ * of the seed voxel and the map.  The cubes of all path points are therefore computed at once, the walk of
+ * polyhedronGenerator::corridorGeneration / corridorInsertGeneration (poly_utils.cpp:391-449, 508-557) reduces to a selection,
+ * and the planes are written in the layout direct_ddp_batch_in_t reads (planes, n_planes, seeds: pass them on with T0 == NULL).
+ * It stands beside the lock-step walk over direct_cluster_polygon_generation_batch(seed, itr_inflate_max, 0) +
+ * direct_cluster_hull_planes_batch and gives, bit for bit, that walk's corridors; it does not reproduce corridors of
+ * is_cluster_on == true, and it has none of that path's capacities (cluster_capacity, the hull's caps): it succeeds where
+ * that path reports an overflow.
+ *   Cube     cubeInflation_cpu (cluster_server_cpu.cpp:257-293): from the single voxel, up to itr_inflate_max rounds over the
+ *            directions Y-, Y+, X-, X+, Z-, Z+; a face moves out by one voxel when it is not on the map's border and the slab
+ *            one voxel beyond it, with the ranges the cube has at that moment, is free; the first round that changes nothing
+ *            is the last.  The seed's own byte is not looked at.  The slab test is one query of the handle's summed-area
+ *            table, which counts map bytes == 1 where the reference tests > 0: THE CALL IS DEFINED ON THE TABLE and equals the
+ *            reference's cube (vertex_idx of direct_cluster_polygon_generation_batch) for maps whose bytes are 0 or 1, which is
+ *            all direct_cluster_map_from_cloud produces; direct_cluster_set_map does not validate its bytes.
+ *   Planes   what direct_cluster_hull_planes_batch returns for the cube's resident cluster, computed by the same code: the six
+ *            lattice planes in ascending (nx, ny, nz, K) order, the half-voxel inflation, the corners of the voxels instead of
+ *            their centres when the cube is one voxel thick along an axis, and the centre as the mean over the planes of the
+ *            first corner on each (NOT the middle of the box).  n_planes is 6.
+ *   Walk     for point i of a row, cur = index * resolution + 0.5 * resolution + map_lower per axis (index2Coord).  A point
+ *            equal to the one visited before it is skipped.  With pop_back (corridorGeneration) a point inside the last-but-one
+ *            polytope removes the last one.  A point for which the corridor is empty, or with
+ *            cur[0]*a + cur[1]*b + cur[2]*c + d > 0.01 for a plane of the latest polytope (isOutsidePolytope; in double, left to
+ *            right, no contraction, on the double planes), appends the cube of its own voxel with seed_coord = cur.  Below a
+ *            resolution of 0.02 that margin admits a voxel centre one voxel outside the cube, as in the reference.  pop_back == 0
+ *            is corridorInsertGeneration started from an empty corridor (extending an existing corridor is not offered).
+ * path_xyz[batch][path_capacity][3] int32 and path_len[batch] in memory kind mem_in are exactly the outputs of
+ * direct_cluster_grid_path_batch, whose device arrays can be passed through.  batch is NOT limited by max_batch.  Outputs in
+ * memory kind `mem`, any may be NULL; planes, seeds and centers are double or float as plane_dtype says (float: one rounding of
+ * the double):
+ *   n_seg[batch]                          polytopes of the corridor (the number NEEDED, also on overflow)
+ *   n_planes[batch][seg_capacity]         6
+ *   planes[batch][seg_capacity][p_max][4] p_max >= 6 is the stride of the optimiser's plane array; rows 6 .. p_max - 1 are zero
+ *   seeds[batch][seg_capacity][3], centers[batch][seg_capacity][3]
+ *   cube_idx[batch][seg_capacity][6]      lo x, y, z, hi x, y, z of every polytope's cube (inclusive voxel indices)
+ *   rtn[batch]                            codes below, per row: a failing row does not affect the others
+ * Every entry from a row's n_seg on is zero, n_planes included.  No output depends on the launch shape.
+ * DIRECT_ERR_INVALID, nothing launched: a handle without a map; a NULL handle, struct, path_xyz or path_len; a non-positive
+ * batch, path_capacity, seg_capacity or itr_inflate_max; p_max < 6; an unknown mem_in, mem or plane_dtype; a resolution that is
+ * not finite and positive; a non-finite map_lower.  DIRECT_ERR_UNSUPPORTED: batch * path_capacity or batch * seg_capacity *
+ * p_max of 2^28 or more.  Runs on the handle's stream and synchronises before it returns; direct_cluster_last_ms covers its
+ * two kernels (not the copies of host arrays).  The call follows the map the handle holds now.  Its workspace (28 B per path
+ * slot) and the staging of host arrays are blocks of its own on the handle, grown on demand, never shrunk and freed in
+ * direct_cluster_destroy; it leaves resident clusters, the grid-path workspace and the distance field alone. */
+#define DIRECT_CUBE_CORRIDOR_OK 0
+#define DIRECT_CUBE_CORRIDOR_OVERFLOW 1 /* more polytopes than seg_capacity: n_seg is the number needed, the first seg_capacity are valid */
+#define DIRECT_CUBE_CORRIDOR_BAD_PATH 2 /* path_len <= 0, path_len > path_capacity (an OVERFLOW row of the path stage), or a voxel outside the map: n_seg 0 */
+typedef struct {
+  int32_t batch, path_capacity;
+  int32_t mem_in;            /* direct_mem_t of path_xyz and path_len */
+  int32_t itr_inflate_max;   /* > 0; paramSet's value without clustering is 1000 */
+  const int32_t* path_xyz;   /* [batch][path_capacity][3] */
+  const int32_t* path_len;   /* [batch] */
+  int32_t pop_back;          /* 1: corridorGeneration's walk, 0: corridorInsertGeneration's from an empty corridor */
+  int32_t seg_capacity;
+  int32_t p_max;             /* >= 6 */
+  int32_t plane_dtype;       /* direct_dtype_t of planes, seeds, centers */
+  double resolution;
+  double map_lower[3];
+} direct_cube_corridor_in_t;
+
+typedef struct {
+  int32_t mem;               /* direct_mem_t: where every array below lives */
+  int32_t reserved;
+  int32_t* n_seg;            /* [batch] or NULL */
+  int32_t* n_planes;         /* [batch][seg_capacity] or NULL */
+  void* planes;              /* [batch][seg_capacity][p_max][4] or NULL */
+  void* seeds;               /* [batch][seg_capacity][3] or NULL */
+  void* centers;             /* [batch][seg_capacity][3] or NULL */
+  int32_t* cube_idx;         /* [batch][seg_capacity][6] or NULL */
+  int32_t* rtn;              /* [batch] or NULL */
+} direct_cube_corridor_out_t;
+
+direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in,
+                                                   direct_cube_corridor_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
- * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch call */
+ * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
