@@ -57,8 +57,8 @@ __global__ void k_hull_src(Dev D, HullDev H, int batch, const int32_t* xyz /* or
     }
     if (bad) atomicOr(&H.he[e].pad0, 1);  // pad0 / overflow were zeroed by the host before this launch
   } else {
-    // resident clusters: only a generation that ended well left a usable cluster (an overflowed one is a truncated
-    // prefix, DIRECT_CLUSTER_OVERFLOW: "not usable"); the count is clamped to the storage whatever the element says
+    // resident clusters: only a generation that ended well left a usable cluster (an overflowed one is a
+    // prefix of its cluster, DIRECT_CLUSTER_OVERFLOW: nothing to build a hull from); the count is clamped to the storage whatever the element says
     const int rt = D.el[e].rtn;
     n = rt == DIRECT_CLUSTER_OK ? D.el[e].n_cluster : 0;
     n = n < 0 ? 0 : (n > D.ccap ? D.ccap : n);

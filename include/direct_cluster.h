@@ -101,14 +101,22 @@ direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, u
 
 /* Return codes per seed (the reference has none: it writes past its buffers instead). */
 #define DIRECT_CLUSTER_OK 0
-#define DIRECT_CLUSTER_OVERFLOW 1  /* cluster_capacity / candidate_capacity exceeded: result truncated, not usable */
+#define DIRECT_CLUSTER_OVERFLOW 1  /* cluster_capacity / candidate_capacity exceeded: the cluster is incomplete (see below) */
 #define DIRECT_CLUSTER_BAD_SEED 2  /* seed voxel outside the map */
 
 /* polygonGeneration for `batch` seeds (host array seeds[batch][3]).  itr_inflate_max / itr_cluster_max as given to
  * paramSet with is_cluster_on (is_cluster_on == false is (1000, 0)).  Outputs in memory kind `mem`, any may be NULL:
  *   vertex_idx[batch][24]       the inflated cube (cluster_server_cpu.cpp:48-60 layout: x 0..7, y 8..15, z 16..23)
  *   cluster_xyz[batch][cluster_capacity][3]   cluster voxels in the reference's order
- *   cluster_num[batch], cluster_iters[batch] (completed rounds of polytopeCluster_cpu), rtn[batch] (codes above) */
+ *   cluster_num[batch], cluster_iters[batch] (completed rounds of polytopeCluster_cpu), rtn[batch] (codes above)
+ * A row that ends with DIRECT_CLUSTER_OVERFLOW (the cube's surface, or a round's accepted candidates, would pass
+ * cluster_capacity; a round has more candidates than candidate_capacity) keeps its vertex_idx, and cluster_num <= cluster_capacity
+ * voxels that are a PREFIX of the cluster the reference would build, in its order.  When the cube's surface alone passes
+ * cluster_capacity the prefix is the first cluster_capacity voxels of the surface and no round has run; otherwise how long a prefix
+ * is not specified (the surface and the rounds completed before the overflow at least, the capacity at most).  cluster_iters counts
+ * the completed rounds only, and the row is not
+ * a cluster to build a hull from (direct_cluster_hull_planes_batch gives a resident row like it no planes).  Codes are per row: the
+ * other rows of the batch are what they would be alone. */
 direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t h, int32_t batch, const int32_t* seeds,
                                                         int32_t itr_inflate_max, int32_t itr_cluster_max, int32_t mem,
                                                         int32_t* vertex_idx, int32_t* cluster_xyz, int32_t* cluster_num,

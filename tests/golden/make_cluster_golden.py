@@ -11,7 +11,13 @@ serialConvexTest (oracle/_ref/libcluster_engine_ref.so, compiled from
                         run with the reference function plugged in.
   cluster_convex_random_12.npz  twelve seeded random scenes (map, inside box, 60 candidates, a 6-voxel cluster) and
                         serialConvexTest of every candidate against the cluster.
-Run from the repo root in the build container: python tests/golden/make_cluster_golden.py"""
+  cluster_shell_classes.npz  the scenes of tests/cluster_shell_lib.py (a box with one stopper per face and obstacles on the
+                        edge rows of its first shell: 4095 ... 18000 candidates in the first round), two clustering rounds each
+                        through the restated loops with the reference function plugged in: per scene the generator's
+                        parameters, seed, vertex_idx, iters, the cluster size after the surface and after every round, every
+                        round's candidate count, the per-range report, the cluster and the SHA-256 of its int32 bytes.
+Run from the repo root in the build container: python tests/golden/make_cluster_golden.py
+(`python tests/golden/make_cluster_golden.py shell` writes cluster_shell_classes.npz alone)"""
 import os
 import sys
 
@@ -21,6 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from direct_amd import problems  # noqa: E402
 from oracle import clusterapi as ca  # noqa: E402
+from tests import cluster_shell_lib as shell  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -77,6 +84,29 @@ def write_random_scenes():
     np.savez_compressed(os.path.join(OUT, "cluster_convex_random_12.npz"), **random_scenes())
 
 
+def write_shell_classes():
+    """cluster_shell_classes.npz; every scene meets the conditions on the inputs and has the candidate count it promises."""
+    reference = ca.ref_lib() is not None
+    names = shell.scene_names()
+    res = shell.run_scenes(names, reference=reference)
+    out = dict(names=np.array(names), reference=np.array(bool(reference)))
+    for n in names:
+        sc, r = shell.scene(n), res[n]
+        bad = shell.unmet_conditions(r)
+        print(shell.format_report(n, r))
+        assert not bad, (n, bad)
+        assert r["n_cand"][0] == sc["expect_candidates"], (n, r["n_cand"], sc["expect_candidates"])
+        out.update({n + "_cube": np.array(sc["cube"], np.int32), n + "_n_shell": np.int32(sc["n_shell"]),
+                    n + "_n_outer": np.int32(sc["n_outer"]), n + "_seed": sc["seed"], n + "_vertex_idx": r["vertex_idx"],
+                    n + "_iters": np.int32(r["iters"]), n + "_sizes": r["sizes"], n + "_n_cand": r["n_cand"],
+                    n + "_report": np.array([[q[c] for c in shell.REPORT_COLUMNS] for q in r["report"]], np.int32),
+                    n + "_sha256": np.array(shell.cluster_digest(r["cluster"])), n + "_cluster": r["cluster"]})
+    path = os.path.join(OUT, "cluster_shell_classes.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1 << 20, "past the size limit of a committed file: store digests for the boundary scenes"
+    print("cluster_shell_classes.npz: %d bytes" % os.path.getsize(path))
+
+
 def main():
     assert ca.ref_lib() is not None, "build oracle/_ref first (make -C oracle _ref)"
     grid, seeds = problems.make_voxel_map((48, 48, 16), seed=11, n_pillars=22, n_boxes=10, n_rings=2)
@@ -99,7 +129,11 @@ def main():
                         cluster_num=num, cluster_xyz=np.concatenate(cls), iters=np.array(its, np.int32))
     print("polygon: clusters", num.tolist(), "iters", its)
     write_random_scenes()
+    write_shell_classes()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["shell"]:
+        write_shell_classes()
+    else:
+        main()
