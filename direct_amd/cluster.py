@@ -178,21 +178,27 @@ class ClusterGenerator:
                                                  cluster.ctypes.data, clu.ctypes.data, cc.ctypes.data, acc.ctypes.data))
         return clu, cc[:n * (n - 1) // 2], acc
 
-    def hull_planes(self, resolution, map_lower, clusters=None, plane_capacity=256, vertex_capacity=1024, batch=None):
+    def hull_planes(self, resolution, map_lower, clusters=None, plane_capacity=256, vertex_capacity=1024, batch=None,
+                    want=("planes", "plane_int", "vertices", "center"), num=None):
         """getConvexPoly's hull + Polyhedron::hrep + polyHrep2Utils (poly_utils.cpp:301-389, 127-206) for a batch of
         clusters.  clusters=None: those of the last polygon_generation, still on the device (`batch` of them);
         otherwise a list of [n][3] voxel-index arrays.  -> dict(planes: list of [P][4], plane_int, vertices: list of
-        [V][3], center [B][3], degenerate, n_planes, n_vertices, rtn)"""
+        [V][3], center [B][3], degenerate, n_planes, n_vertices, rtn).  want: which of planes / plane_int / vertices /
+        center are asked for; the C-ABI gets NULL for the others (no capacity applies to them) and the dict None.  num:
+        cluster_num as the C-ABI is to see it, instead of the clusters' lengths (it clamps to [0, cluster_capacity])."""
+        assert set(want) <= {"planes", "plane_int", "vertices", "center"}
         lower = np.ascontiguousarray(map_lower, np.float64)
         if clusters is not None:
             B = len(clusters)
             xyz = np.zeros((B, self.ccap, 3), np.int32)
-            num = np.zeros(B, np.int32)
+            given, num = num, np.zeros(B, np.int32)
             for b, c in enumerate(clusters):
                 c = np.ascontiguousarray(c, np.int32).reshape(-1, 3)
                 assert len(c) <= self.ccap
                 xyz[b, :len(c)] = c
                 num[b] = len(c)
+            if given is not None:
+                num[:] = given
             px, pn = xyz.ctypes.data, num.ctypes.data
         else:
             B, px, pn = int(batch), None, None
@@ -201,13 +207,15 @@ class ClusterGenerator:
         vt = np.zeros((B, vertex_capacity, 3), np.float64)
         ctr = np.zeros((B, 3), np.float64)
         npl, nv, deg, rtn = (np.zeros(B, np.int32) for _ in range(4))
+        ptr = lambda a, k: a.ctypes.data if k in want else None
         _check(_lib().direct_cluster_hull_planes_batch(self.h, B, abi.MEM_HOST, px, pn, float(resolution), lower.ctypes.data,
-                                                       int(plane_capacity), int(vertex_capacity), abi.MEM_HOST, pl.ctypes.data,
-                                                       pi.ctypes.data, npl.ctypes.data, vt.ctypes.data, nv.ctypes.data,
-                                                       ctr.ctypes.data, deg.ctypes.data, rtn.ctypes.data))
-        cut = lambda a, n, cap: [a[b, :min(int(n[b]), cap)].copy() for b in range(B)]
-        return dict(planes=cut(pl, npl, plane_capacity), plane_int=cut(pi, npl, plane_capacity),
-                    vertices=cut(vt, nv, vertex_capacity), center=ctr, degenerate=deg, n_planes=npl, n_vertices=nv, rtn=rtn)
+                                                       int(plane_capacity), int(vertex_capacity), abi.MEM_HOST, ptr(pl, "planes"),
+                                                       ptr(pi, "plane_int"), npl.ctypes.data, ptr(vt, "vertices"), nv.ctypes.data,
+                                                       ptr(ctr, "center"), deg.ctypes.data, rtn.ctypes.data))
+        cut = lambda a, n, cap, k: [a[b, :min(int(n[b]), cap)].copy() for b in range(B)] if k in want else None
+        return dict(planes=cut(pl, npl, plane_capacity, "planes"), plane_int=cut(pi, npl, plane_capacity, "plane_int"),
+                    vertices=cut(vt, nv, vertex_capacity, "vertices"), center=ctr if "center" in want else None,
+                    degenerate=deg, n_planes=npl, n_vertices=nv, rtn=rtn)
 
     def grid_paths(self, starts, goals, path_capacity=4096, max_rounds=0, want_dist=False, mem="host"):
         """Optimal 26-connected voxel paths on the handle's map for a batch of (start, goal) voxel-index pairs

@@ -29,6 +29,7 @@
 namespace hull {
 
 typedef long long i64;
+typedef __int128 i128;  // the one product of edge_test that outgrows 64 bits on maps wider than 724 voxels
 
 constexpr int kCandCap = 2048;     // candidates per cluster (24 KB of LDS in the edge kernel)
 constexpr int kRawCap = 8192;      // facet planes reported by edges, duplicates included (a few hundred for real clusters;
@@ -74,6 +75,13 @@ HULL_HD bool line_extreme(const Lines& L, int qx, int qy, int qz) {
 // Is the candidate pair (a, b) a hull edge with no candidate strictly between its ends?  1: yes, ir / il are the
 // candidates that span the wedge (ir clockwise-most, il counter-clockwise-most, looking along b - a); 0: no;
 // 2: every other candidate lies in ONE half-plane through the line (a flat point set).
+//
+// Magnitudes, with D the diameter of the point set in lattice units (D <= 2048 sqrt(3) < 2^11.8 on the largest map, 1024
+// voxels per axis): |e1| <= |d| <= D, |e2| = |d| |e1| <= D^2, so |u| <= D^2 and |v| <= D^3.  The cross products
+// Ru v - Rv u are differences of two terms below D^5 < 2^59 each and fit 64 bits on every map.  The dot product of the
+// tie-break, Ru u + Rv v, reaches D^6 ~ 2^71: in 64 bits it wrapped from D = 2^10.5 on (a box 725 voxels wide: its edge
+// along x sees the corners of the opposite face at v = 8 * 725^3), turned a zero-width wedge into "surrounded" and lost
+// the box's edges while the call still returned DIRECT_HULL_OK.  It is carried in 128 bits; no extent limit remains.
 template <typename CoordFn>
 HULL_HD int edge_test(CoordFn P, int nc, int a, int b, int& ir, int& il) {
   int ax, ay, az, bx, by, bz;
@@ -109,7 +117,7 @@ HULL_HD int edge_test(CoordFn P, int nc, int a, int b, int& ir, int& il) {
     }
     const i64 cR = Ru * v - Rv * u, cL = Lu * v - Lv * u;
     if (cR >= 0 && cL <= 0) {  // inside the wedge - or opposite to a wedge of zero width
-      if (cR == 0 && cL == 0 && Ru * u + Rv * v < 0) return 0;
+      if (cR == 0 && cL == 0 && (i128)Ru * u + (i128)Rv * v < 0) return 0;
     } else if (cR > 0 && cL > 0) {  // beyond the counter-clockwise end, still within 180 degrees of the other end
       Lu = u;
       Lv = v;

@@ -153,6 +153,10 @@ direct_status_t direct_cluster_convex_test(direct_cluster_handle_t h, const uint
  * centre (an argmin over residuals that are all ~1e-16; here the first corner, in cluster order, on the plane).
  * Vertices are the corners of the hull in cluster order (quickhull's vertex buffer may also hold boundary points that
  * are not corners; cdd's H-rep does not depend on them).
+ * EXTENT: no limit beyond the map's (1024 voxels per axis).  With D the diameter of a cluster in lattice units
+ * (D < 2^11.8) the orientation tests stay below 2^60; the one product that reaches D^6 - it overflowed 64 bits from a
+ * width of 725 voxels on - is carried in 128 bits (hull_core.h).  A cluster never comes back DIRECT_HULL_OK with planes
+ * other than its hull's.
  *
  * cluster_xyz == NULL: the clusters of the last polygon_generation_batch, still resident on the device (no copy of
  * the voxels in either direction; `batch` may not exceed that call's, and a seed whose generation did not end with

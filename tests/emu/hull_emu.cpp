@@ -50,6 +50,7 @@ extern "C" int hull_emu(int n, const int32_t* idx, double res, const double* low
   }
   const int nc = (int)cx.size();
   if (n_cand_out) *n_cand_out = nc;
+  if (overflow) return 1;  // the device still runs the pair phase on the first kCandCap candidates; the code is the same
   auto P = [&](int i, int& x, int& y, int& z) { x = cx[i]; y = cy[i]; z = cz[i]; };
   std::vector<int> first(nc, -1), isv(nc, 0);
   std::vector<i64> raw;

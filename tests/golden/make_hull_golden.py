@@ -4,6 +4,10 @@ flat ones, the vertex buffer and the triangles getConvexHull(points, true, false
 getConvexPoly builds (poly_utils.cpp:301-389); hull_quickhull_live_10.npz: the same for ten clusters the restated
 polygonGeneration grows on a seeded random map (tests/test_hull.py).  Needs oracle/_ref (the reference's sources, oracle/Makefile):
     python tests/golden/make_hull_golden.py
+hull_shapes.npz: the ORACLE'S answer (oracle/hull_ref.c) for every shape of tests/hull_shape_lib.py - large extents, voxel
+shells, flat discs -, so that its slow runs (the larger shells) never happen inside a test; where oracle/_ref is
+built every full-dimensional shape is pinned against the reference's quickhull first.  Needs no oracle/_ref:
+    python tests/golden/make_hull_golden.py shapes
 """
 import os
 import sys
@@ -12,6 +16,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 from oracle import clusterapi, hullapi  # noqa: E402
+from tests import hull_shape_lib as shapes  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -41,6 +46,7 @@ def main():
     np.savez_compressed(os.path.join(HERE, "hull_quickhull_16.npz"), **out)
     print("wrote", len(clusters), "clusters")
     write_live_clusters()
+    write_shapes()
 
 
 def live_clusters(n=10):
@@ -72,5 +78,21 @@ def write_live_clusters():
     np.savez_compressed(os.path.join(HERE, "hull_quickhull_live_10.npz"), **live_clusters())
 
 
+def write_shapes():
+    hullapi.build()
+    out = {}
+    for name in shapes.SHAPES:
+        cl = shapes.build(name)
+        r = hullapi.hull_planes(cl, shapes.RES, shapes.LOWER, plane_cap=shapes.PLANE_CAP, vert_cap=shapes.VERT_CAP)
+        assert r["rc"] in (0, 3), (name, r["rc"])
+        if r["rc"] == 0 and hullapi.ref_lib() is not None:
+            hullapi.check_against_quickhull(hullapi.lattice_points(cl, r["degenerate"]), r["plane_int"], r["vert_q"])
+        out["%s/n" % name] = len(cl)
+        for k in ("plane_int", "planes", "vert_q", "vertices", "center", "degenerate", "rc"):
+            out["%s/%s" % (name, k)] = r[k]
+        print("%-14s n %6d rc %d planes %4d corners %4d" % (name, len(cl), r["rc"], r["n_planes"], r["n_vertices"]), flush=True)
+    np.savez_compressed(os.path.join(HERE, "hull_shapes.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    write_shapes() if sys.argv[1:] == ["shapes"] else main()

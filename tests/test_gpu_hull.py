@@ -1,7 +1,8 @@
 """direct_cluster_hull_planes_batch (include/direct_cluster.h; poly_utils.cpp:127-206, 282-389) on the device against the
 oracle (oracle/hull_ref.c, pinned against the reference's quickhull by tests/test_hull.py): planes, lattice planes,
 corners and centre bit for bit; committed quickhull golden vectors; device-resident chaining seeds -> clusters ->
-planes -> DDP."""
+planes -> DDP; the shapes of tests/hull_shape_lib.py (large extents, shells, flat discs, capacities, reuse, optional outputs)
+against the oracle results committed in tests/golden/hull_shapes.npz."""
 import os
 
 import numpy as np
@@ -9,6 +10,7 @@ import pytest
 
 from direct_amd import abi, cluster, problems, solver
 from oracle import clusterapi, hullapi
+from tests import hull_shape_lib as shapes
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -221,4 +223,125 @@ def test_hull_input_guards(built):
     assert np.array_equal(ro["clusters"][0], cl_full[:n])          # a valid prefix, never stale storage
     ho = gen.hull_planes(RES, LOWER, batch=1)
     assert ho["rtn"][0] == cluster.HULL_OVERFLOW and ho["n_planes"][0] == 0
+    gen.close()
+
+
+# ---- shapes beyond grown blobs (tests/hull_shape_lib.py; oracle results committed in tests/golden/hull_shapes.npz) ----
+CCAP = 20480          # holds the R = 30.5 shell (20024 voxels); box_cap fills it exactly
+SMALL = [n for n, s in shapes.SHAPES.items() if s[1] == shapes.SMALL_MAP]
+CAPS = dict(plane_capacity=shapes.PLANE_CAP, vertex_capacity=shapes.VERT_CAP)
+
+
+@pytest.fixture(scope="module")
+def fix():
+    return np.load(os.path.join(GOLD, "hull_shapes.npz"))
+
+
+def small_gen(max_batch):
+    return cluster.ClusterGenerator(shapes.SMALL_MAP, max_batch=max_batch, cluster_capacity=CCAP, candidate_capacity=64)
+
+
+def rows_equal(a, i, b, j):
+    """row i of call a and row j of call b are the same answer (only what the call defines: n_planes planes, n_vertices corners)"""
+    for k in ("rtn", "degenerate", "n_planes", "n_vertices"):
+        assert a[k][i] == b[k][j], k
+    for k in ("plane_int", "planes", "vertices"):
+        assert np.array_equal(a[k][i], b[k][j]), k
+    if a["rtn"][i] == cluster.HULL_OK:
+        assert np.array_equal(a["center"][i], b["center"][j])
+
+
+def test_shapes_match_the_committed_oracle_bitwise(built, fix):
+    """Voxel shells (hundreds of candidates and planes), flat discs in z, x and y above the 256-point chunk of k_hull_cand
+    and of the corner compaction, a disc one voxel away from flat, the diagonal sheet, a cluster that fills the capacity, and
+    the shell with more line-extreme points than hull::kCandCap in the middle of them: one call, every row bit for bit."""
+    names = SMALL[:9] + [shapes.OVERFLOW_SHAPE] + SMALL[9:]
+    gen = small_gen(len(names))
+    dev = gen.hull_planes(RES, LOWER, clusters=[shapes.build(n) for n in names], **CAPS)
+    gen.close()
+    for b, n in enumerate(names):
+        shapes.assert_same(shapes.device_row(dev, b), shapes.fixture_row(fix, n), n)
+    b = names.index(shapes.OVERFLOW_SHAPE)
+    assert dev["rtn"][b] == cluster.HULL_OVERFLOW and dev["n_planes"][b] == 0 and dev["n_vertices"][b] == 0
+
+
+def test_one_call_with_every_return_code_equals_the_rows_alone(built, fix):
+    ball, shell = shapes.build("ball_6.5"), shapes.build(shapes.OVERFLOW_SHAPE)
+    bad = ball.copy()
+    bad[len(bad) // 3] = [shapes.SMALL_MAP[0], 2, 2]
+    cases = [ball, shapes.build("disc_25.5_z"), shapes.sheet(), bad, shell, np.zeros((0, 3), np.int32), ball, shapes.box_cap()]
+    num = [len(c) for c in cases]
+    num[6], num[7] = -3, CCAP + 7                    # below zero: an empty row; above the capacity: clamped to it
+    assert len(cases[7]) == CCAP
+    gen = small_gen(len(cases))
+    dev = gen.hull_planes(RES, LOWER, clusters=cases, num=num, **CAPS)
+    gen.close()
+    assert list(dev["rtn"]) == [cluster.HULL_OK, cluster.HULL_OK, cluster.HULL_FLAT, cluster.HULL_BAD_VOXEL, cluster.HULL_OVERFLOW,
+                                cluster.HULL_FLAT, cluster.HULL_FLAT, cluster.HULL_OK]
+    for b, n in ((0, "ball_6.5"), (1, "disc_25.5_z"), (2, "sheet"), (4, shapes.OVERFLOW_SHAPE), (7, "box_cap")):
+        shapes.assert_same(shapes.device_row(dev, b), shapes.fixture_row(fix, n), n)
+    for b in (3, 5, 6):
+        assert dev["n_planes"][b] == 0 and dev["n_vertices"][b] == 0
+    one = small_gen(1)
+    for b in range(len(cases)):
+        rows_equal(dev, b, one.hull_planes(RES, LOWER, clusters=[cases[b]], num=[num[b]], **CAPS), 0)
+    one.close()
+
+
+def test_a_reused_handle_answers_like_a_fresh_one(built, fix):
+    """Slot 0 holds the R = 10.5 shell (344 candidates, 192 corners), then a 3 x 3 x 3 box (8 candidates), then a flat disc
+    (56 candidates of which 32 are corners): lattice lines, first partners and corner flags of the earlier call must be gone."""
+    box = np.array([[x, y, z] for x in range(4, 7) for y in range(5, 8) for z in range(2, 5)])
+    seq = [(shapes.build("ball_10.5"), shapes.fixture_row(fix, "ball_10.5")), (box, hullapi.hull_planes(box, RES, LOWER)),
+           (shapes.build("disc_10.5_z"), shapes.fixture_row(fix, "disc_10.5_z"))]
+    gen = small_gen(2)
+    for cl, ref in seq:
+        dev = gen.hull_planes(RES, LOWER, clusters=[cl], **CAPS)
+        shapes.assert_same(shapes.device_row(dev, 0), ref)
+        fresh = small_gen(2)
+        rows_equal(dev, 0, fresh.hull_planes(RES, LOWER, clusters=[cl], **CAPS), 0)
+        fresh.close()
+    gen.close()
+
+
+def test_capacities_count_only_for_outputs_that_were_asked_for(built, fix):
+    cl, ref = shapes.build("ball_10.5"), shapes.fixture_row(fix, "ball_10.5")
+    assert ref["n_vertices"] == 192 and ref["n_planes"] == 122
+    gen = small_gen(1)
+    # vertex capacity below the corner count: reported, the count exact, the corners that fit and all planes delivered
+    d = gen.hull_planes(RES, LOWER, clusters=[cl], plane_capacity=shapes.PLANE_CAP, vertex_capacity=100)
+    assert d["rtn"][0] == cluster.HULL_OVERFLOW and d["n_vertices"][0] == 192 and d["n_planes"][0] == 122
+    assert np.array_equal(d["vertices"][0], ref["vertices"][:100])
+    assert np.array_equal(d["plane_int"][0], ref["plane_int"]) and np.array_equal(d["planes"][0], ref["planes"])
+    assert np.array_equal(d["center"][0], ref["center"])
+    # the same without the vertices: their capacity does not count
+    d = gen.hull_planes(RES, LOWER, clusters=[cl], plane_capacity=shapes.PLANE_CAP, vertex_capacity=100,
+                        want=("planes", "plane_int", "center"))
+    assert d["rtn"][0] == cluster.HULL_OK and d["n_vertices"][0] == 192 and d["vertices"] is None
+    assert np.array_equal(d["plane_int"][0], ref["plane_int"]) and np.array_equal(d["planes"][0], ref["planes"])
+    assert np.array_equal(d["center"][0], ref["center"])
+    # neither planes nor plane_int: the plane capacity does not count, the plane count stays exact
+    d = gen.hull_planes(RES, LOWER, clusters=[cl], plane_capacity=8, vertex_capacity=shapes.VERT_CAP, want=("vertices", "center"))
+    assert d["rtn"][0] == cluster.HULL_OK and d["n_planes"][0] == 122 and d["n_vertices"][0] == 192
+    assert np.array_equal(d["vertices"][0], ref["vertices"]) and np.array_equal(d["center"][0], ref["center"])
+    # plane_int alone still makes the capacity count
+    d = gen.hull_planes(RES, LOWER, clusters=[cl], plane_capacity=8, vertex_capacity=shapes.VERT_CAP, want=("plane_int",))
+    assert d["rtn"][0] == cluster.HULL_OVERFLOW and d["n_planes"][0] == 122
+    assert np.array_equal(d["plane_int"][0], ref["plane_int"][:8])
+    gen.close()
+
+
+def test_clusters_as_wide_as_the_largest_map_match_the_oracle(built, fix):
+    """Extents of 255 .. 1022 voxels on a 1023 x 1023 x 64 map, with the pair on either side of the extent at which
+    hull::edge_test's tie-break product left 64 bits (hull_shape_lib).  The handle: 0.27 GB summed-area table, 67 MB map and
+    scratch copy, and per batch row 67 MB of flags, 268 MB of keys and 38 MB of lattice lines: 1.2 GB at max_batch 2, allocated
+    and never touched apart from the lines (two fills of 75 MB per call)."""
+    gen = cluster.ClusterGenerator(shapes.BIG_MAP, max_batch=2, cluster_capacity=16, candidate_capacity=64)
+    for i in range(0, len(shapes.EXTENT), 2):
+        names = shapes.EXTENT[i:i + 2]
+        dev = gen.hull_planes(RES, LOWER, clusters=[shapes.build(n) for n in names], **CAPS)
+        for b, n in enumerate(names):
+            ref = shapes.fixture_row(fix, n)
+            assert ref["rc"] == 0 and ref["n_planes"] == 6 and ref["n_vertices"] == 8
+            shapes.assert_same(shapes.device_row(dev, b), ref, n)
     gen.close()

@@ -3,12 +3,16 @@
 live on fresh clusters -, the geometric properties no implementation may break, and the device algorithm's predicates
 and formulas (direct_amd/csrc/hull_core.h, built for the host by tests/emu/hull_emu.cpp) against the oracle, bit for bit.
 PARITY: pinned for the facet planes and the corner set (quickhull); cdd's row order and per-plane vertex choice are
-not reproducible and are defined in include/direct_cluster.h."""
+not reproducible and are defined in include/direct_cluster.h.
+Beyond grown blobs: the shapes of tests/hull_shape_lib.py (map-wide extents, voxel shells, flat discs, the candidate
+capacity), whose oracle results are committed in tests/golden/hull_shapes.npz."""
 import os
 
 import numpy as np
+import pytest
 
 from oracle import clusterapi, hullapi
+from tests import hull_shape_lib as shapes
 from tests.emu import hullemu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -122,3 +126,51 @@ def test_edge_cases():
     assert cut["rc"] == 1 and cut["n_planes"] == full["n_planes"]
     e = hullemu.hull_planes(g0, RES, LOWER, plane_cap=4)
     assert e["rc"] == 1 and e["n_planes"] == full["n_planes"] and np.array_equal(e["plane_int"], full["plane_int"][:4])
+
+
+_FIX = []
+
+
+def shape_fixture():
+    if not _FIX:
+        _FIX.append(np.load(os.path.join(GOLD, "hull_shapes.npz")))
+    return _FIX[0]
+
+
+@pytest.mark.parametrize("name", list(shapes.SHAPES) + [shapes.OVERFLOW_SHAPE])
+def test_shapes_host_build_matches_the_committed_oracle_bitwise(name):
+    """Every shape of hull_shape_lib through the host build of hull_core.h: planes, corners and centre equal the oracle's
+    committed answer bit for bit, and the answer has the properties of a hull.  The ext_* cases from ext_box725 up
+    returned code 0 with 5 planes and 4 corners while hull::edge_test's tie-break product was formed in 64 bits."""
+    cl = shapes.build(name)
+    ref = shapes.fixture_row(shape_fixture(), name)
+    got = hullemu.hull_planes(cl, shapes.RES, shapes.LOWER, plane_cap=shapes.PLANE_CAP, vert_cap=shapes.VERT_CAP)
+    shapes.assert_same(got, ref, name)
+    if name == shapes.OVERFLOW_SHAPE:
+        assert got["n_cand"] == 2048 and len(cl) == 20024      # hull::kCandCap, reached by the shell's line-extreme points
+    else:
+        assert len(cl) == int(shape_fixture()["%s/n" % name])
+    if ref["rc"] == 0:
+        assert (RES, tuple(LOWER)) == (shapes.RES, tuple(shapes.LOWER))
+        properties(cl, got)
+
+
+def test_shapes_committed_oracle_results_are_reproduced_live():
+    """the shapes the oracle answers within a second, recomputed: the fixture is what oracle/hull_ref.c gives today"""
+    for name, (_, _, fast) in shapes.SHAPES.items():
+        if fast:
+            r = hullapi.hull_planes(shapes.build(name), shapes.RES, shapes.LOWER, plane_cap=shapes.PLANE_CAP, vert_cap=shapes.VERT_CAP)
+            shapes.assert_same(r, shapes.fixture_row(shape_fixture(), name), name)
+
+
+def test_shape_sizes_reach_their_paths():
+    """the sizes the shapes were chosen for: flat discs above the 256-point chunk of the compactions, shells with hundreds
+    of candidates, the overflow pair on either side of 2^63"""
+    assert [len(shapes.disc(r)) for r in (10.5, 25.5, 40.5)] == [349, 2053, 5169]
+    assert [len(shapes.ball_shell(r)) for r in (6.5, 10.5, 15.5)] == [728, 2168, 4688]
+    e = shapes.OVERFLOW_AT
+    assert 64 * (e - 1) ** 6 < 2 ** 63 <= 64 * e ** 6             # v = 8 E^3 on the box's x edge (hull_shape_lib, hull_core.h)
+    for name in ("ball_6.5", "ball_10.5", "ball_15.5", "disc_10.5_z", "disc_25.5_z", "disc_40.5_z"):
+        g = hullemu.hull_planes(shapes.build(name), shapes.RES, shapes.LOWER, plane_cap=shapes.PLANE_CAP)
+        assert g["n_cand"] == {"ball_6.5": 168, "ball_10.5": 344, "ball_15.5": 696, "disc_10.5_z": 56, "disc_25.5_z": 120,
+                               "disc_40.5_z": 192}[name]
