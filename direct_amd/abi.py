@@ -152,6 +152,20 @@ class CubeCorridorOut(C.Structure):  # direct_cube_corridor_out_t (include/direc
 CUBE_CORRIDOR_OUTPUTS = ("n_seg", "n_planes", "planes", "seeds", "centers", "cube_idx", "rtn")   # the arrays of CubeCorridorOut
 
 
+class GridPathClearIn(C.Structure):  # direct_grid_path_clear_in_t (include/direct_cluster.h)
+    _fields_ = [("batch", C.c_int32), ("path_capacity", C.c_int32), ("max_rounds", C.c_int32), ("mem", C.c_int32),
+                ("starts", C.c_void_p), ("goals", C.c_void_p), ("min_d2", C.c_int32), ("n_penalty", C.c_int32), ("penalty", C.c_void_p)]
+
+
+class GridPathClearOut(C.Structure):  # direct_grid_path_clear_out_t (include/direct_cluster.h)
+    _fields_ = [("path_xyz", C.c_void_p), ("path_len", C.c_void_p), ("path_cost", C.c_void_p), ("dist", C.c_void_p),
+                ("stats", C.c_void_p), ("rtn", C.c_void_p), ("path_d2", C.c_void_p), ("path_min_d2", C.c_void_p)]
+
+
+GRID_PATH_CLEAR_OUTPUTS = ("path_xyz", "path_len", "path_cost", "dist", "stats", "rtn", "path_d2", "path_min_d2")   # the arrays of GridPathClearOut
+GRID_PATH_MAX_PENALTY = 65536   # entries of a penalty table at most
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

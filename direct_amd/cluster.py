@@ -34,6 +34,7 @@ class PlanCheckOut(C.Structure):  # direct_plan_check_out_t
 
 PlanClearIn, PlanClearOut = abi.PlanClearIn, abi.PlanClearOut  # direct_plan_clear_in_t, direct_plan_clear_out_t
 CubeCorridorIn, CubeCorridorOut = abi.CubeCorridorIn, abi.CubeCorridorOut  # direct_cube_corridor_in_t, direct_cube_corridor_out_t
+GridPathClearIn, GridPathClearOut = abi.GridPathClearIn, abi.GridPathClearOut  # direct_grid_path_clear_in_t, direct_grid_path_clear_out_t
 
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
@@ -41,7 +42,7 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
            "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
-           "direct_cluster_cube_corridor_batch")
+           "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -78,8 +79,19 @@ def _lib():
         L.direct_cluster_get_distance_field.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_plan_clearance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_cube_corridor_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_grid_path_clear_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
+
+
+def clearance_penalty_table(weight, soft_radius_vox):
+    """A penalty table for grid_paths_clear, indexed by the stored D2: weight * (1 - sqrt(d2) / soft_radius_vox)^2 for every
+    d2 < soft_radius_vox^2 (the entry at 0 is included; it is never read for a free voxel).  Pure NumPy, float64; beyond the table
+    the penalty is 0."""
+    r = float(soft_radius_vox)
+    n = int(np.ceil(r * r)) if r > 0 else 0
+    d2 = np.arange(n, dtype=np.float64)
+    return float(weight) * (1.0 - np.sqrt(d2) / r) ** 2 if n else np.zeros(0, np.float64)
 
 
 def _check(st):
@@ -248,6 +260,42 @@ class ClusterGenerator:
                                                      dist.ctypes.data if want_dist else None, stats.ctypes.data, rtn.ctypes.data))
         return dict(paths=[xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)], path_len=n, path_cost=cost, rtn=rtn, stats=stats,
                     dist=dist)
+
+    def grid_paths_clear(self, starts, goals, min_d2=0, penalty=None, path_capacity=4096, max_rounds=0, want_dist=False, mem="host"):
+        """grid_paths on the resident distance field (direct_cluster_grid_path_clear_batch; build_distance_field must have run since
+        the map last changed): a move enters only voxels with stored D2 >= min_d2 (voxel^2), and entering voxel v costs the step
+        weight plus penalty[D2[v]] (a float64 table, e.g. clearance_penalty_table; None: no penalty), two rounded additions in that
+        order.  min_d2=0, penalty=None is grid_paths.  Returns what grid_paths returns for the same `mem`, plus
+        path_d2 (host: a list of [n] int32 arrays beside paths; device: [B][path_capacity] int32), the stored D2 of each path
+        voxel, and path_min_d2 [B], the minimum over the path without its start (DIST_NONE for a path of one voxel or none)."""
+        starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
+        goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+        assert starts.shape == goals.shape and mem in ("host", "device")
+        B, cap = starts.shape[0], int(path_capacity)
+        pen = None if penalty is None else np.ascontiguousarray(penalty, np.float64).reshape(-1)
+        par = GridPathClearIn(batch=B, path_capacity=cap, max_rounds=int(max_rounds), starts=starts.ctypes.data, goals=goals.ctypes.data,
+                              min_d2=int(min_d2), n_penalty=0 if pen is None else len(pen), penalty=None if pen is None else pen.ctypes.data)
+        if mem == "device":
+            import torch
+            assert not want_dist
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
+            out = dict(path_xyz=z((B, cap, 3), torch.int32), path_len=z(B, torch.int32), path_cost=z(B, torch.float64),
+                       stats=z((B, 2), torch.int32), rtn=z(B, torch.int32), path_d2=z((B, cap), torch.int32), path_min_d2=z(B, torch.int32))
+            torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
+            par.mem = abi.MEM_DEVICE
+            o = GridPathClearOut(*[out[k].data_ptr() if k in out else None for k in abi.GRID_PATH_CLEAR_OUTPUTS])
+            _check(_lib().direct_cluster_grid_path_clear_batch(self.h, C.addressof(par), C.addressof(o)))
+            return out
+        out = dict(path_xyz=np.zeros((B, cap, 3), np.int32), path_len=np.zeros(B, np.int32), path_cost=np.zeros(B, np.float64),
+                   dist=np.zeros((B, int(np.prod(self.dims))), np.float64) if want_dist else None, stats=np.zeros((B, 2), np.int32),
+                   rtn=np.zeros(B, np.int32), path_d2=np.zeros((B, cap), np.int32), path_min_d2=np.zeros(B, np.int32))
+        par.mem = abi.MEM_HOST
+        o = GridPathClearOut(*[None if out[k] is None else out[k].ctypes.data for k in abi.GRID_PATH_CLEAR_OUTPUTS])
+        _check(_lib().direct_cluster_grid_path_clear_batch(self.h, C.addressof(par), C.addressof(o)))
+        n, xyz, d2 = out["path_len"], out.pop("path_xyz"), out["path_d2"]
+        out["paths"] = [xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)]
+        out["path_d2"] = [d2[b, :min(int(n[b]), cap)].copy() for b in range(B)]
+        return out
 
     def check_plans(self, n_seg, T, map_lower, resolution, bez=None, poly=None, depth=8, margin=0.0, t_from=None, outside_blocks=False, count=False):
         """Solved plans against the map the handle holds now (direct_cluster_plan_check_batch): for every plan whether the curve

@@ -30,6 +30,7 @@
 
 #include "../../include/direct_cluster.h"
 #include "cube_corridor_math.h"
+#include "grid_path_clear_math.h"
 #include "grid_path_math.h"
 #include "host_stage.h"
 #include "hull_core.h"
@@ -980,6 +981,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 
 #include "hull_kernels.h"
 #include "grid_path.h"
+#include "grid_path_clear.h"
 #include "map_cloud.h"
 #include "plan_check.h"
 #include "dist_field.h"
@@ -1026,6 +1028,8 @@ struct direct_cluster_handle_s {
   int32_t* dist[2] = {nullptr, nullptr};  // the distance field (in dist[0]) and its ping-pong partner, allocated by the first distance_field
   unsigned long long* dist_cnt = nullptr;  // [2] the counters behind its stats
   bool dist_valid = false;  // dist[0] describes the map the handle holds
+  int32_t dist_cap2 = 0;    // the cap2 the field in dist[0] was built with (DIRECT_DIST_NONE: uncapped): grid_path_clear_batch's cap rule
+  double* path_pen = nullptr;  // [gp::kMaxPenalty] the penalty table of grid_path_clear_batch, allocated by its first call with a table
   hs::Block clear_ws;  // workspace of plan_clearance_batch (start times, per-slot minima), grown on demand
   hs::Block clear_io;  // device staging of its host arrays, grown on demand
   hs::Block cube_ws;   // workspace of cube_corridor_batch (the cube of every path slot, the walks' stacks), grown on demand
@@ -1040,6 +1044,27 @@ hipError_t rebuild_sat(direct_cluster_handle_t h) {
   hipLaunchKernelGGL(k_sat_fill, dim3(1024), dim3(256), 0, h->stream, D);
   for (int axis = 2; axis >= 0; axis--) hipLaunchKernelGGL(k_sat_scan, dim3(256), dim3(256), 0, h->stream, D, axis);
   return hipGetLastError();
+}
+
+// The workspace the two grid-path calls share (fields, flags, counters), allocated by whichever comes first: all or nothing, as
+// the hull's scratch.
+hipError_t path_workspace(direct_cluster_handle_t h) {
+  if (h->have_path) return hipSuccess;
+  const Dev& D = h->D;
+  const size_t B = h->cfg.max_batch;
+  PathDev N = {};
+  N.X = D.max_x; N.Y = D.max_y; N.Z = D.max_z; N.YZ = D.max_yz; N.G = D.G;
+  N.tx = gp::tiles_along(N.X); N.ty = gp::tiles_along(N.Y); N.tz = gp::tiles_along(N.Z);
+  N.ntiles = N.tx * N.ty * N.tz;
+  N.map = h->map;
+  const hipError_t ae = hs::alloc_all(h->allocs, {
+      hs::want(&N.field, B * (size_t)N.G * sizeof(double)), hs::want(&N.flag[0], B * (size_t)N.ntiles),
+      hs::want(&N.flag[1], B * (size_t)N.ntiles), hs::want(&N.ends, B * 6 * sizeof(int)), hs::want(&N.pending, B * sizeof(int)),
+      hs::want(&N.rounds, B * sizeof(int)), hs::want(&N.visits, B * sizeof(int))});
+  if (ae != hipSuccess) return ae;
+  h->P = N;
+  h->have_path = true;
+  return hipSuccess;
 }
 }  // namespace
 
@@ -1420,23 +1445,10 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
   if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
   if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  const Dev& D = h->D;
   PathDev& P = h->P;
-  const size_t B = h->cfg.max_batch, nb = (size_t)batch;
-  if (!h->have_path) {  // all or nothing, as the hull's scratch
-    PathDev N = {};
-    N.X = D.max_x; N.Y = D.max_y; N.Z = D.max_z; N.YZ = D.max_yz; N.G = D.G;
-    N.tx = gp::tiles_along(N.X); N.ty = gp::tiles_along(N.Y); N.tz = gp::tiles_along(N.Z);
-    N.ntiles = N.tx * N.ty * N.tz;
-    N.map = h->map;
-    const hipError_t ae = hs::alloc_all(h->allocs, {
-        hs::want(&N.field, B * (size_t)N.G * sizeof(double)), hs::want(&N.flag[0], B * (size_t)N.ntiles),
-        hs::want(&N.flag[1], B * (size_t)N.ntiles), hs::want(&N.ends, B * 6 * sizeof(int)), hs::want(&N.pending, B * sizeof(int)),
-        hs::want(&N.rounds, B * sizeof(int)), hs::want(&N.visits, B * sizeof(int))});
-    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
-    P = N;
-    h->have_path = true;
-  }
+  const size_t nb = (size_t)batch;
+  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
   // one block for the read-back ring (a scratch slice, needed whatever `mem` is) and the staging of host outputs (nothing is filled)
   const size_t cap = (size_t)path_capacity;
   const size_t sz[5] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t)};
@@ -1571,6 +1583,7 @@ direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: ") + hipGetErrorString(e));
   h->dist_valid = true;
+  h->dist_cap2 = A.cap2;
   if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)(int32_t)(cnt[1] & 0xffffffffull); }
   return DIRECT_OK;
 }
@@ -1693,6 +1706,88 @@ direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, co
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("cube_corridor_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, const direct_grid_path_clear_in_t* in,
+                                                     direct_grid_path_clear_out_t* out) {
+  if (!h || !in || !out || !in->starts || !in->goals) return cfail(DIRECT_ERR_INVALID, "null argument");
+  // what the arguments alone decide comes first, then what the handle holds
+  if (in->batch <= 0) return cfail(DIRECT_ERR_INVALID, "batch must be positive");
+  if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
+  if (in->n_penalty < 0 || in->n_penalty > gp::kMaxPenalty) return cfail(DIRECT_ERR_INVALID, "n_penalty outside [0, 65536]");
+  if (in->n_penalty > 0 && !in->penalty) return cfail(DIRECT_ERR_INVALID, "a NULL penalty requires n_penalty == 0");
+  for (int i = 0; i < in->n_penalty; i++)
+    if (!std::isfinite(in->penalty[i]) || !(in->penalty[i] >= 0.0)) return cfail(DIRECT_ERR_INVALID, "penalty entries must be finite and not negative");
+  if (in->batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
+  // a stored cap2 means "at least cap2": neither the floor nor the table may tell values at or above it apart (an uncapped
+  // field has cap2 = DIRECT_DIST_NONE, which refuses nothing)
+  if (in->min_d2 > h->dist_cap2 || in->n_penalty > h->dist_cap2)
+    return cfail(DIRECT_ERR_INVALID, "min_d2 or n_penalty above the cap2 the distance field was built with");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: workspace allocation: ") + hipGetErrorString(ae));
+  if (in->n_penalty > 0 && !h->path_pen) {
+    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->path_pen, (size_t)gp::kMaxPenalty * sizeof(double))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: table allocation: ") + hipGetErrorString(ae));
+  }
+  PathDev& P = h->P;
+  PathClearDev C = {};
+  C.d2 = h->dist[0];
+  C.pen = in->n_penalty > 0 ? h->path_pen : nullptr;
+  C.n_pen = in->n_penalty; C.min_d2 = in->min_d2;
+  // one block for the two read-back rings (scratch slices, needed whatever `mem` is) and the staging of host outputs
+  const int batch = in->batch;
+  const size_t nb = (size_t)batch, cap = (size_t)in->path_capacity;
+  const size_t sz[7] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t),
+                        nb * cap * sizeof(int32_t), nb * sizeof(int32_t)};
+  void* const user[7] = {out->path_xyz, out->path_len, out->path_cost, out->stats, out->rtn, out->path_d2, out->path_min_d2};
+  void* dev[7];
+  hs::Stage st(in->mem == DIRECT_MEM_HOST);
+  hs::stage_scratch(st, &P.ring, nb * cap * sizeof(int));
+  hs::stage_scratch(st, &C.ring_d2, nb * cap * sizeof(int));
+  for (int i = 0; i < 7; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
+  CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
+  P.cap = (int)cap;
+  std::vector<int> ends(nb * 6);
+  for (size_t b = 0; b < nb; b++)
+    for (int a = 0; a < 3; a++) { ends[6 * b + a] = in->starts[3 * b + a]; ends[6 * b + 3 + a] = in->goals[3 * b + a]; }
+  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (in->n_penalty > 0)
+    CHIP_TRY(hipMemcpyAsync(h->path_pen, in->penalty, (size_t)in->n_penalty * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
+  CHIP_TRY(hipGetLastError());
+  // the rounds of direct_cluster_grid_path_batch: separate launches, enqueued eight at a time, then ONE read-back
+  constexpr int kRoundsPerCheck = 8;
+  const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
+  std::vector<int> pending(nb);
+  int done = 0;
+  while (done < lim) {
+    const int n = (int)std::min<long long>(kRoundsPerCheck, lim - done);
+    for (int r = 0; r < n; r++) hipLaunchKernelGGL(k_path_clear_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, C, done + r);
+    CHIP_TRY(hipGetLastError());
+    done += n;
+    CHIP_TRY(hipMemcpyAsync(pending.data(), P.pending, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    CHIP_TRY(hipStreamSynchronize(h->stream));
+    bool live = false;
+    for (int v : pending) live |= v == done;
+    if (!live) break;
+  }
+  hipLaunchKernelGGL(k_path_clear_trace, dim3(batch), dim3(64), 0, h->stream, P, C, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
+                     (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (int32_t*)dev[6]);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(st, h->stream, e);
+  if (e == hipSuccess && out->dist)
+    e = hipMemcpyAsync(out->dist, P.field, nb * (size_t)P.G * sizeof(double),
+                       in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 

@@ -487,11 +487,77 @@ typedef struct {
 direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in,
                                                    direct_cube_corridor_out_t* out);
 
+/* ---- clearance-aware grid paths: the path stage on the resident distance field (no reference counterpart) ------------
+ * direct_cluster_grid_path_batch with two additions read from the distance field the handle holds: a hard floor ("never
+ * closer than this") and a soft cost ("prefer open space, pay for proximity").  Optimal paths on a voxel graph hug corners
+ * and walls; this call is the one stage that can give a plan air before the corridor is built.  Let D2[v] be the STORED
+ * field value of voxel v (direct_cluster_distance_field), in voxel^2 units.
+ *   Graph   the 26 neighbours.  A move goes INTO a voxel v inside the map with map byte 0 AND D2[v] >= min_d2.  D2 is 0
+ *           exactly on occupied voxels, so for min_d2 <= 1 this is the graph of direct_cluster_grid_path_batch.  The start
+ *           voxel's byte, D2 and penalty are never looked at, as there.
+ *   Cost    pen(v) = penalty[D2[v]] if D2[v] < n_penalty, else 0.0.  d(start) = 0 and
+ *             d(v) = fl( min over the neighbours u of fl(d(u) + w(u, v)) + pen(v) ),
+ *           w the three constants of the plain call: TWO rounded double additions per move, in this order, the step weight
+ *           first, then the penalty of the voxel entered.  pen(v) does not depend on u and a -> fl(a + p) is monotone, so
+ *           this equals min_u fl(fl(d(u) + w) + pen(v)): the minimum may be taken before the second addition, and that is
+ *           the form the kernel uses.  path_cost = d(goal) is the left-to-right fold (((0 + w_1) + pen_1) + w_2) + pen_2 ...
+ *           along the emitted path, to the bit.
+ *   Path    read backwards from the goal: the predecessor of v is the first neighbour u, in the ascending (dx, dy, dz)
+ *           order of the plain call, with fl(fl(d(u) + w) + pen(v)) == d(v) as doubles.
+ * One result, whatever the launch shape.  Every value the relaxation holds is the fold of some walk from the start, hence an
+ * upper bound of d.  The map a -> fl(fl(a + w) + p) is monotone and >= a because w > 0 and p >= 0; so a heap Dijkstra with
+ * these two additions settles voxels in non-decreasing order of d, and by induction along that order the tiled relaxation,
+ * whatever order its tiles run in and whichever of a neighbour's old or new values it reads, ends on the same field.
+ * Costs never fall along a walk, so a voxel whose value exceeds the goal's current value cannot lie on an optimal path to
+ * the goal: pruning by that value stays valid.  d falls STRICTLY along the read-back because w >= 1, so the trace ends.
+ * Inputs: batch, starts, goals (HOST, [batch][3]), path_capacity, max_rounds and mem are those of
+ * direct_cluster_grid_path_batch; min_d2 >= 0; penalty a HOST array of n_penalty doubles, each finite and >= 0,
+ * 0 <= n_penalty <= 65536, NULL only with n_penalty == 0.
+ * Outputs in memory kind `mem`, any may be NULL: path_xyz, path_len, path_cost, dist, stats and rtn with the layouts, the
+ * exactness contract and the DIRECT_GRID_PATH_* codes of the plain call (NO_PATH also covers a goal with D2 < min_d2 that is
+ * not the start), and
+ *   path_d2[batch][path_capacity]  the stored D2 of each emitted path voxel (the start's included),
+ *   path_min_d2[batch]             the minimum of D2 over ALL voxels of the path except the start - the whole path also on
+ *                                  OVERFLOW, as path_len; DIRECT_DIST_NONE for a path of length 1 and where there is no path.
+ * DIRECT_ERR_INVALID, nothing launched: what the plain call refuses; a NULL struct; min_d2 < 0; n_penalty outside
+ * [0, 65536]; a NULL penalty with n_penalty > 0; a penalty entry that is NaN, infinite or negative; a handle without a map
+ * or without a VALID distance field (a stale field is refused as direct_cluster_plan_clearance_batch refuses it, never
+ * rebuilt silently); and, on a field built with cap_vox > 0 (cap2 = cap_vox^2), min_d2 > cap2 or n_penalty > cap2: a stored
+ * cap2 means "at least cap2", and the call never gives that value two meanings.
+ * The call reuses the plain call's workspace (allocated by whichever of the two comes first) and adds the table on the
+ * device (512 KiB) and a second read-back ring.  It leaves the map, the distance field, resident clusters and every other
+ * workspace alone; direct_cluster_last_ms covers it, direct_cluster_set_stream is honoured. */
+typedef struct {
+  int32_t batch, path_capacity;
+  int32_t max_rounds;        /* 0: the library's default */
+  int32_t mem;               /* direct_mem_t of every output */
+  const int32_t* starts;     /* HOST [batch][3] */
+  const int32_t* goals;      /* HOST [batch][3] */
+  int32_t min_d2;            /* >= 0, voxel^2 */
+  int32_t n_penalty;         /* 0 .. 65536 */
+  const double* penalty;     /* HOST [n_penalty], or NULL with n_penalty == 0 */
+} direct_grid_path_clear_in_t;
+
+typedef struct {
+  int32_t* path_xyz;         /* [batch][path_capacity][3] or NULL */
+  int32_t* path_len;         /* [batch] or NULL */
+  double* path_cost;         /* [batch] or NULL */
+  double* dist;              /* [batch][max_x*max_y*max_z] or NULL */
+  int32_t* stats;            /* [batch][2] or NULL */
+  int32_t* rtn;              /* [batch] or NULL */
+  int32_t* path_d2;          /* [batch][path_capacity] or NULL */
+  int32_t* path_min_d2;      /* [batch] or NULL */
+} direct_grid_path_clear_out_t;
+
+direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, const direct_grid_path_clear_in_t* in,
+                                                     direct_grid_path_clear_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
- * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch call */
+ * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch /
+ * grid_path_clear_batch call */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
