@@ -166,6 +166,20 @@ GRID_PATH_CLEAR_OUTPUTS = ("path_xyz", "path_len", "path_cost", "dist", "stats",
 GRID_PATH_MAX_PENALTY = 65536   # entries of a penalty table at most
 
 
+class GridPathFanIn(C.Structure):  # direct_grid_path_fan_in_t (include/direct_cluster.h)
+    _fields_ = [("n_src", C.c_int32), ("n_goal", C.c_int32), ("path_capacity", C.c_int32), ("max_rounds", C.c_int32), ("mem", C.c_int32),
+                ("sources", C.c_void_p), ("goals", C.c_void_p), ("goal_src", C.c_void_p), ("min_d2", C.c_int32), ("n_penalty", C.c_int32),
+                ("penalty", C.c_void_p)]
+
+
+class GridPathFanOut(C.Structure):  # direct_grid_path_fan_out_t (include/direct_cluster.h)
+    _fields_ = [("path_xyz", C.c_void_p), ("path_len", C.c_void_p), ("path_cost", C.c_void_p), ("rtn", C.c_void_p),
+                ("path_d2", C.c_void_p), ("path_min_d2", C.c_void_p), ("dist", C.c_void_p), ("stats", C.c_void_p)]
+
+
+GRID_PATH_FAN_OUTPUTS = ("path_xyz", "path_len", "path_cost", "rtn", "path_d2", "path_min_d2", "dist", "stats")   # the arrays of GridPathFanOut
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

@@ -35,6 +35,7 @@ class PlanCheckOut(C.Structure):  # direct_plan_check_out_t
 PlanClearIn, PlanClearOut = abi.PlanClearIn, abi.PlanClearOut  # direct_plan_clear_in_t, direct_plan_clear_out_t
 CubeCorridorIn, CubeCorridorOut = abi.CubeCorridorIn, abi.CubeCorridorOut  # direct_cube_corridor_in_t, direct_cube_corridor_out_t
 GridPathClearIn, GridPathClearOut = abi.GridPathClearIn, abi.GridPathClearOut  # direct_grid_path_clear_in_t, direct_grid_path_clear_out_t
+GridPathFanIn, GridPathFanOut = abi.GridPathFanIn, abi.GridPathFanOut  # direct_grid_path_fan_in_t, direct_grid_path_fan_out_t
 
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
@@ -42,7 +43,7 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
            "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
-           "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch")
+           "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -80,6 +81,7 @@ def _lib():
         L.direct_cluster_plan_clearance_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_cube_corridor_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_grid_path_clear_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_grid_path_fan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -295,6 +297,52 @@ class ClusterGenerator:
         n, xyz, d2 = out["path_len"], out.pop("path_xyz"), out["path_d2"]
         out["paths"] = [xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)]
         out["path_d2"] = [d2[b, :min(int(n[b]), cap)].copy() for b in range(B)]
+        return out
+
+    def grid_paths_fan(self, sources, goals, goal_src=None, min_d2=0, penalty=None, path_capacity=4096, max_rounds=0, want_dist=False,
+                       mem="host"):
+        """Many goals from few starts (direct_cluster_grid_path_fan_batch): ONE field per source, relaxed as far as its worst goal
+        needs, and one read-back per goal - per goal the very bytes grid_paths (min_d2 <= 1 and penalty None or empty: neutral mode)
+        or grid_paths_clear (anything else) returns for the pair (sources[goal_src[j]], goals[j]).  sources [S][3] with S <= max_batch,
+        goals [n][3] with n unlimited, goal_src [n] (None: all goals belong to the one source).  Returns what grid_paths /
+        grid_paths_clear return for the same `mem`, per goal (path_d2 and path_min_d2 in clear mode only), with stats [S][2] and
+        dist [S][X*Y*Z] per SOURCE; mem="device" gives tensors in the C-ABI's layout, for cube_corridors to read in place."""
+        sources = np.ascontiguousarray(sources, np.int32).reshape(-1, 3)
+        goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+        gs = None if goal_src is None else np.ascontiguousarray(goal_src, np.int32).reshape(-1)
+        assert mem in ("host", "device") and (gs is None or len(gs) == len(goals))
+        S, n, cap = sources.shape[0], goals.shape[0], int(path_capacity)
+        pen = None if penalty is None or len(penalty) == 0 else np.ascontiguousarray(penalty, np.float64).reshape(-1)
+        clear = not (int(min_d2) <= 1 and pen is None)
+        par = GridPathFanIn(n_src=S, n_goal=n, path_capacity=cap, max_rounds=int(max_rounds), sources=sources.ctypes.data,
+                            goals=goals.ctypes.data, goal_src=None if gs is None else gs.ctypes.data, min_d2=int(min_d2),
+                            n_penalty=0 if pen is None else len(pen), penalty=None if pen is None else pen.ctypes.data)
+        if mem == "device":
+            import torch
+            assert not want_dist
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
+            out = dict(path_xyz=z((n, cap, 3), torch.int32), path_len=z(n, torch.int32), path_cost=z(n, torch.float64),
+                       stats=z((S, 2), torch.int32), rtn=z(n, torch.int32))
+            if clear:
+                out.update(path_d2=z((n, cap), torch.int32), path_min_d2=z(n, torch.int32))
+            torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
+            par.mem = abi.MEM_DEVICE
+            o = GridPathFanOut(*[out[k].data_ptr() if k in out else None for k in abi.GRID_PATH_FAN_OUTPUTS])
+            _check(_lib().direct_cluster_grid_path_fan_batch(self.h, C.addressof(par), C.addressof(o)))
+            return out
+        out = dict(path_xyz=np.zeros((n, cap, 3), np.int32), path_len=np.zeros(n, np.int32), path_cost=np.zeros(n, np.float64),
+                   dist=np.zeros((S, int(np.prod(self.dims))), np.float64) if want_dist else None, stats=np.zeros((S, 2), np.int32),
+                   rtn=np.zeros(n, np.int32))
+        if clear:
+            out.update(path_d2=np.zeros((n, cap), np.int32), path_min_d2=np.zeros(n, np.int32))
+        par.mem = abi.MEM_HOST
+        o = GridPathFanOut(*[None if out.get(k) is None else out[k].ctypes.data for k in abi.GRID_PATH_FAN_OUTPUTS])
+        _check(_lib().direct_cluster_grid_path_fan_batch(self.h, C.addressof(par), C.addressof(o)))
+        ln, xyz = out["path_len"], out.pop("path_xyz")
+        out["paths"] = [xyz[b, :min(int(ln[b]), cap)].copy() for b in range(n)]
+        if clear:
+            d2 = out["path_d2"]
+            out["path_d2"] = [d2[b, :min(int(ln[b]), cap)].copy() for b in range(n)]
         return out
 
     def check_plans(self, n_seg, T, map_lower, resolution, bez=None, poly=None, depth=8, margin=0.0, t_from=None, outside_blocks=False, count=False):

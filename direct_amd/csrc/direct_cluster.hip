@@ -31,6 +31,7 @@
 #include "../../include/direct_cluster.h"
 #include "cube_corridor_math.h"
 #include "grid_path_clear_math.h"
+#include "grid_path_fan_math.h"
 #include "grid_path_math.h"
 #include "host_stage.h"
 #include "hull_core.h"
@@ -982,6 +983,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "hull_kernels.h"
 #include "grid_path.h"
 #include "grid_path_clear.h"
+#include "grid_path_fan.h"
 #include "map_cloud.h"
 #include "plan_check.h"
 #include "dist_field.h"
@@ -1034,6 +1036,9 @@ struct direct_cluster_handle_s {
   hs::Block clear_io;  // device staging of its host arrays, grown on demand
   hs::Block cube_ws;   // workspace of cube_corridor_batch (the cube of every path slot, the walks' stacks), grown on demand
   hs::Block cube_in, cube_out;  // device staging of its host inputs / host outputs (two memory kinds: two blocks), grown on demand
+  hs::Block fan_ws;    // workspace of grid_path_fan_batch (goals, their grouping, bounds, one read-back ring or two per goal), grown on demand
+  hs::Block fan_out;   // device staging of its host outputs, grown on demand
+  int fan_bound_every = 1;  // rounds between two k_fan_bound launches: 1 or 8 (DIRECT_CLUSTER_FAN_BOUND_EVERY: experiments)
 };
 
 namespace {
@@ -1066,6 +1071,32 @@ hipError_t path_workspace(direct_cluster_handle_t h) {
   h->have_path = true;
   return hipSuccess;
 }
+
+template <bool Clear>
+hipError_t fan_rounds(direct_cluster_handle_t h, const PathClearDev& C, const FanDev& F, long long lim, int* rounds_done) {
+  // the rounds of direct_cluster_grid_path_batch over (tiles, sources): separate launches, enqueued eight at a time, then ONE
+  // read-back; k_fan_bound goes in front of every round or of every batch of rounds (fan_bound_every)
+  const PathDev& P = h->P;
+  std::vector<int> pending((size_t)F.n_src);
+  int done = 0;
+  while (done < lim) {
+    const int n = (int)std::min<long long>(gp::kFanRoundsPerCheck, lim - done);
+    for (int r = 0; r < n; r++) {
+      if (r % h->fan_bound_every == 0) hipLaunchKernelGGL(k_fan_bound<Clear>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
+      hipLaunchKernelGGL(k_fan_relax<Clear>, dim3(P.ntiles, F.n_src), dim3(256), 0, h->stream, P, C, (const double*)F.bound, done + r);
+    }
+    hipError_t e = hipGetLastError();
+    done += n;
+    *rounds_done = done;
+    if (e == hipSuccess) e = hipMemcpyAsync(pending.data(), P.pending, pending.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) return e;
+    bool live = false;
+    for (int v : pending) live |= v == done;
+    if (!live) break;
+  }
+  return hipSuccess;
+}
 }  // namespace
 
 extern "C" {
@@ -1095,6 +1126,7 @@ direct_status_t direct_cluster_create(const direct_cluster_config_t* cfg, direct
   direct_cluster_handle_t h = new direct_cluster_handle_s();
   h->cfg = *cfg;
   if (const char* ev = getenv("DIRECT_CLUSTER_CONVEX_GRID")) h->convex_grid = atoi(ev) > 0 ? atoi(ev) : h->convex_grid;
+  if (const char* ev = getenv("DIRECT_CLUSTER_FAN_BOUND_EVERY")) h->fan_bound_every = atoi(ev) == gp::kFanRoundsPerCheck ? gp::kFanRoundsPerCheck : 1;
   Dev& D = h->D;
   D.max_x = cfg->max_x; D.max_y = cfg->max_y; D.max_z = cfg->max_z; D.max_yz = cfg->max_y * cfg->max_z;
   D.G = cfg->max_x * cfg->max_y * cfg->max_z;
@@ -1138,7 +1170,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
-                       &h->cube_out})
+                       &h->cube_out, &h->fan_ws, &h->fan_out})
     hs::release(*b);
   hs::destroy(h->ev);
   delete h;
@@ -1788,6 +1820,115 @@ direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, 
                        in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, const direct_grid_path_fan_in_t* in,
+                                                   direct_grid_path_fan_out_t* out) {
+  if (!h || !in || !out || !in->sources || !in->goals) return cfail(DIRECT_ERR_INVALID, "null argument");
+  // what the arguments alone decide comes first, then what the handle holds
+  if (in->n_src < 1) return cfail(DIRECT_ERR_INVALID, "n_src must be positive");
+  if (in->n_goal < 1) return cfail(DIRECT_ERR_INVALID, "n_goal must be positive");
+  if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
+  if (in->n_penalty < 0 || in->n_penalty > gp::kMaxPenalty) return cfail(DIRECT_ERR_INVALID, "n_penalty outside [0, 65536]");
+  if (in->n_penalty > 0 && !in->penalty) return cfail(DIRECT_ERR_INVALID, "a NULL penalty requires n_penalty == 0");
+  for (int i = 0; i < in->n_penalty; i++)
+    if (!std::isfinite(in->penalty[i]) || !(in->penalty[i] >= 0.0)) return cfail(DIRECT_ERR_INVALID, "penalty entries must be finite and not negative");
+  if (!in->goal_src && in->n_src != 1) return cfail(DIRECT_ERR_INVALID, "a NULL goal_src requires n_src == 1");
+  if (in->goal_src)
+    for (int j = 0; j < in->n_goal; j++)
+      if (in->goal_src[j] < 0 || in->goal_src[j] >= in->n_src) return cfail(DIRECT_ERR_INVALID, "goal_src entry outside [0, n_src)");
+  const bool clear = !(in->min_d2 <= 1 && in->n_penalty == 0);
+  if (!clear && (out->path_d2 || out->path_min_d2))
+    return cfail(DIRECT_ERR_INVALID, "path_d2 and path_min_d2 must be NULL in neutral mode (min_d2 <= 1, n_penalty == 0)");
+  if (in->n_src > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "n_src exceeds the handle's max_batch");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (clear) {
+    if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
+    if (in->min_d2 > h->dist_cap2 || in->n_penalty > h->dist_cap2)  // direct_cluster_grid_path_clear_batch's cap rule
+      return cfail(DIRECT_ERR_INVALID, "min_d2 or n_penalty above the cap2 the distance field was built with");
+  }
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ae));
+  if (in->n_penalty > 0 && !h->path_pen) {
+    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->path_pen, (size_t)gp::kMaxPenalty * sizeof(double))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: table allocation: ") + hipGetErrorString(ae));
+  }
+  PathDev& P = h->P;
+  PathClearDev C = {};
+  if (clear) {
+    C.d2 = h->dist[0];
+    C.pen = in->n_penalty > 0 ? h->path_pen : nullptr;
+    C.n_pen = in->n_penalty; C.min_d2 = in->min_d2;
+  }
+  const size_t ns = (size_t)in->n_src, ng = (size_t)in->n_goal, cap = (size_t)in->path_capacity;
+  // the goals, their sources and the grouping by source (a counting sort: the goals of a source in the caller's order), one array
+  std::vector<int> meta(3 * ng + ng + ng + ns + 1), ends(ns * 6);
+  int *m_goal = meta.data(), *m_src = m_goal + 3 * ng, *m_order = m_src + ng, *m_off = m_order + ng;
+  std::copy(in->goals, in->goals + 3 * ng, m_goal);
+  for (size_t j = 0; j < ng; j++) m_src[j] = in->goal_src ? in->goal_src[j] : 0;
+  std::fill(m_off, m_off + ns + 1, 0);
+  for (size_t j = 0; j < ng; j++) m_off[m_src[j] + 1]++;
+  for (size_t s = 0; s < ns; s++) m_off[s + 1] += m_off[s];
+  {
+    std::vector<int> at(m_off, m_off + ns);
+    for (size_t j = 0; j < ng; j++) m_order[at[m_src[j]]++] = (int)j;
+  }
+  for (size_t s = 0; s < ns; s++)
+    for (int a = 0; a < 3; a++) ends[6 * s + a] = ends[6 * s + 3 + a] = in->sources[3 * s + a];  // k_path_init's (start, goal) = (source, source)
+  // Two blocks, both or neither: the workspace (host inputs and scratch, whatever `mem` is) and the staging of host outputs.
+  FanDev F = {};
+  F.n_src = in->n_src; F.n_goal = in->n_goal;
+  int* d_meta = nullptr;
+  hs::Stage sw(true), so(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(sw, &d_meta, meta.data(), meta.size() * sizeof(int));
+  hs::stage_scratch(sw, &F.bound, ns * sizeof(double));
+  hs::stage_scratch(sw, &F.ring, out->path_xyz ? ng * cap * sizeof(int) : 0);
+  hs::stage_scratch(sw, &F.ring_d2, out->path_d2 ? ng * cap * sizeof(int) : 0);
+  const size_t sz[7] = {ng * cap * 3 * sizeof(int32_t), ng * sizeof(int32_t), ng * sizeof(double), ng * sizeof(int32_t),
+                        ng * cap * sizeof(int32_t), ng * sizeof(int32_t), ns * 2 * sizeof(int32_t)};
+  void* const user[7] = {out->path_xyz, out->path_len, out->path_cost, out->rtn, out->path_d2, out->path_min_d2, out->stats};
+  void* dev[7];
+  for (int i = 0; i < 7; i++) hs::stage_out(so, &dev[i], user[i], sz[i]);
+  hipError_t ue = hs::stage_upload(sw, h->fan_ws, h->stream);
+  if (ue == hipSuccess) ue = hs::stage_upload(so, h->fan_out, h->stream);
+  if (ue != hipSuccess) {
+    (void)hipStreamSynchronize(h->stream);
+    hs::release(h->fan_ws);
+    hs::release(h->fan_out);
+    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ue));
+  }
+  F.goals = d_meta; F.gsrc = d_meta + 3 * ng; F.order = F.gsrc + ng; F.off = F.order + ng;
+  P.cap = (int)cap;
+  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), ns * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (in->n_penalty > 0)
+    CHIP_TRY(hipMemcpyAsync(h->path_pen, in->penalty, (size_t)in->n_penalty * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), in->n_src), dim3(256), 0, h->stream, P);
+  CHIP_TRY(hipGetLastError());
+  const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
+  int done = 0;
+  hipError_t e = clear ? fan_rounds<true>(h, C, F, lim, &done) : fan_rounds<false>(h, C, F, lim, &done);
+  if (e == hipSuccess) {
+    if (clear)
+      hipLaunchKernelGGL(k_fan_trace<true>, dim3(in->n_goal), dim3(64), 0, h->stream, P, C, F, done, (int32_t*)dev[0], (int32_t*)dev[1],
+                         (double*)dev[2], (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5]);
+    else
+      hipLaunchKernelGGL(k_fan_trace<false>, dim3(in->n_goal), dim3(64), 0, h->stream, P, C, F, done, (int32_t*)dev[0], (int32_t*)dev[1],
+                         (double*)dev[2], (int32_t*)dev[3], (int32_t*)nullptr, (int32_t*)nullptr);
+    if (dev[6]) hipLaunchKernelGGL(k_fan_stats, dim3(1), dim3(64), 0, h->stream, P, in->n_src, (int32_t*)dev[6]);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(so, h->stream, e);
+  if (e == hipSuccess && out->dist)
+    e = hipMemcpyAsync(out->dist, P.field, ns * (size_t)P.G * sizeof(double),
+                       in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 

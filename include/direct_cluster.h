@@ -552,12 +552,88 @@ typedef struct {
 direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, const direct_grid_path_clear_in_t* in,
                                                      direct_grid_path_clear_out_t* out);
 
+/* ---- shared-start grid paths: one field per source, any number of goals (no reference counterpart) ------------------
+ * The batches this project is built for nearly always share an endpoint: one vehicle at one place now, many candidate goals.
+ * The field d of the two calls above depends on the START alone (they read the goal only to prune, and the read-back never
+ * writes the field), so one relaxation per distinct start serves any number of goals.  This call does that, with the plain
+ * cost or the clearance-aware one, and returns per goal THE VERY BYTES the pairwise call returns.
+ *   Sources  sources[n_src][3], HOST, 1 <= n_src <= max_batch: a source owns one field slot of the workspace the pairwise
+ *            calls use (allocated by whichever path call comes first).
+ *   Goals    goals[n_goal][3], HOST, n_goal >= 1 and NOT limited by max_batch; goal_src[n_goal] (HOST) names each goal's
+ *            source, NULL means all 0 (then n_src must be 1).  A source may have no goal at all.
+ *   Modes    NEUTRAL is min_d2 <= 1 && n_penalty == 0: the graph and the cost of direct_cluster_grid_path_batch, no distance
+ *            field needed (a stale or missing one is not looked at); path_d2 and path_min_d2 must then be NULL.  Any other
+ *            parameters are CLEAR mode: the graph, the two-addition cost and the predecessor rule of
+ *            direct_cluster_grid_path_clear_batch, min_d2 / n_penalty / penalty as there.
+ * Definition.  For goal j with s = goal_src[j]: path_xyz[j], path_len[j], path_cost[j], rtn[j] (and, in clear mode, path_d2[j]
+ * and path_min_d2[j]) are the bytes the pairwise call - the plain one in neutral mode, the clear one otherwise, with the same
+ * path_capacity - returns for the single query (sources[s], goals[j]).  Why: with every goal's optimal path exact in the field
+ * (below), the predecessor rule reads only values below d(goal), all exact, and picks the lowest matching neighbour: one path.
+ * Per-goal codes, the existing five, each for that goal only except where a whole source is named:
+ *   BAD_ENDPOINT  the goal is outside the map, or its source is (a source outside the map computes nothing: ALL its goals);
+ *   NO_PATH       as in the pairwise calls, a goal that is occupied or below the floor and is not its source included;
+ *   OVERFLOW      the needed length and the valid cost are returned, as there;
+ *   ROUND_LIMIT   EVERY goal of a source that is still changing when max_rounds is reached (the one code that may differ
+ *                 from the pairwise call's: a source relaxes as far as its WORST goal needs);
+ *   a goal equal to its source is OK with length 1 and cost 0, whatever the voxel's byte.
+ * Pruning.  bound(s) is the maximum of d_s(goal) over the ELIGIBLE goals of s: inside the map, source inside the map, and
+ * either equal to the source or enterable (map byte 0 and, in clear mode, D2 >= min_d2).  A goal known to be NO_PATH before
+ * anything runs is not eligible and does not switch pruning off for its group; a source without an eligible goal has bound 0
+ * and relaxes nothing.  Costs never fall along a walk, so a voxel above the bound lies on no optimal path to any goal of s.
+ * Outputs in memory kind `mem`, any may be NULL: the per-goal arrays above, and per source
+ *   dist[n_src][max_x*max_y*max_z]  exact wherever the true distance is <= the largest path_cost among the source's eligible
+ *           goals (if one of them is unreachable: the whole connected component of the source); elsewhere any value >= the
+ *           true distance, +inf included;
+ *   stats[n_src][2]  rounds in which the source had an active tile, tile visits: diagnostic, NOT deterministic.
+ * Everything but stats, and dist where it is not exact, is independent of the launch shape, of how the goals are grouped and
+ * of their order: one call with all goals, the goals split over several calls and a permuted goal list give identical bytes
+ * per goal.
+ * DIRECT_ERR_INVALID, nothing launched.  From the arguments alone, checked first: a NULL struct, sources or goals; n_src < 1;
+ * n_goal < 1; path_capacity <= 0; max_rounds < 0; a bad mem; min_d2 < 0; the table checks of the clear call; a NULL goal_src
+ * with n_src != 1; a goal_src entry outside [0, n_src); path_d2 or path_min_d2 in neutral mode.  From the handle: n_src >
+ * max_batch; no map; and in clear mode everything direct_cluster_grid_path_clear_batch refuses - a stale or missing distance
+ * field, min_d2 or n_penalty above the cap2 the field was built with.
+ * Workspace: the fields, flags and counters of the pairwise calls serve the n_src slots; blocks of this call's own, grown on
+ * demand and freed in direct_cluster_destroy, hold the goals, their grouping, the bounds and 4 B x path_capacity x n_goal per
+ * read-back ring (one for path_xyz, one for path_d2); host outputs go through one staging block.  It leaves the map, the
+ * distance field, resident clusters and every other workspace alone; direct_cluster_last_ms covers it,
+ * direct_cluster_set_stream is honoured.
+ * OUT OF SCOPE: many starts to one goal.  The cost is a left-to-right fold of rounded additions from the START, and a move
+ * pays for the voxel it enters; a field relaxed backwards from a shared goal folds the same terms in the other order, so a
+ * reversed fan is not bit-equal to the pairwise call, and none is offered. */
+typedef struct {
+  int32_t n_src, n_goal, path_capacity;
+  int32_t max_rounds;        /* 0: the library's default */
+  int32_t mem;               /* direct_mem_t of every output */
+  const int32_t* sources;    /* HOST [n_src][3] */
+  const int32_t* goals;      /* HOST [n_goal][3] */
+  const int32_t* goal_src;   /* HOST [n_goal], index into sources; NULL means all 0 (then n_src must be 1) */
+  int32_t min_d2;            /* >= 0, voxel^2 */
+  int32_t n_penalty;         /* 0 .. 65536 */
+  const double* penalty;     /* HOST [n_penalty], or NULL with n_penalty == 0 */
+} direct_grid_path_fan_in_t;
+
+typedef struct {
+  int32_t* path_xyz;         /* [n_goal][path_capacity][3] or NULL */
+  int32_t* path_len;         /* [n_goal] or NULL */
+  double* path_cost;         /* [n_goal] or NULL */
+  int32_t* rtn;              /* [n_goal] or NULL, DIRECT_GRID_PATH_* */
+  int32_t* path_d2;          /* [n_goal][path_capacity] or NULL; NULL in neutral mode */
+  int32_t* path_min_d2;      /* [n_goal] or NULL; NULL in neutral mode */
+  double* dist;              /* [n_src][max_x*max_y*max_z] or NULL */
+  int32_t* stats;            /* [n_src][2] or NULL */
+} direct_grid_path_fan_out_t;
+
+direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, const direct_grid_path_fan_in_t* in,
+                                                   direct_grid_path_fan_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
  * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch /
- * grid_path_clear_batch call */
+ * grid_path_clear_batch / grid_path_fan_batch call (the fan: its init, bounds, rounds, read-back and stats kernels with the
+ * read-backs of the round counters between them, not the copies of host arrays) */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
