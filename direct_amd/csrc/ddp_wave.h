@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "ddp_tables.h"
+#include "sched_ticket.h"
 
 #if defined(DIRECT_EMULATE)
 #include <cmath>
@@ -3885,7 +3886,9 @@ struct Wave {
   // ---- one trip of the outer loop (DDP:295-412).  Sets st.done when the loop breaks. ------------
   // helper != 0: no trip at all - this wave joins what trajectory b's owner has open: 1 its line search (fwd_pass),
   // 2 its backward sweep (bwd_front_run)
-  DDP_DEV void iterate_once(int helper = 0) {
+  // part (sched_ticket.h; owners only): kPartBackward ends the trip behind the retry loop, kPartSearch enters it there - the
+  // two halves of a trip as the ticket scheduler hands them out.  Between them lie TrajState and arrays in HBM only.
+  DDP_DEV void iterate_once(int helper = 0, int part = sched::kPartWhole) {
     // The helpers' half of a shared backward sweep: a waiting wave (helper == 2) joins the sweep that trajectory b's owner
     // has open; in the tests' forced split the owner itself plays the helper before each of its sweeps.
     BwdShare* bsf = bshare_slot();
@@ -3894,10 +3897,14 @@ struct Wave {
     if (helper == 2 && (bsf == nullptr || !bs_enter(bsf, f_tag, f_cur, f_infeas, f_mu))) return;
 #if defined(DDP_TIMELINE) && !defined(DIRECT_EMULATE)
     unsigned long long* tl_ = (!helper && B.tl != nullptr && st.fwd_passes < kTimelineDepth) ? B.tl + ((size_t)b * kTimelineDepth + st.fwd_passes) * 4 : nullptr;
-    if (tl_ != nullptr && threadIdx.x == 0) { tl_[0] = __builtin_amdgcn_s_memrealtime(); tl_[3] = 0; }
+    if (part != sched::kPartSearch) {
+      if (tl_ != nullptr && threadIdx.x == 0) { tl_[0] = __builtin_amdgcn_s_memrealtime(); tl_[3] = 0; }
+    } else if (tl_ != nullptr && threadIdx.x == 0) {  // the wait between the two halves, in bits 32.. of the split count
+      tl_[3] |= (__builtin_amdgcn_s_memrealtime() - tl_[1]) << 32;
+    }
     tl_split_ = 0;
 #endif
-    if (helper != 1) {
+    if (helper != 1 && part != sched::kPartSearch) {
 #pragma unroll 1
       while (true) {  // DDP:297-310
         if (!helper) {
@@ -3915,7 +3922,15 @@ struct Wave {
           return;
         }
         DDP_DBG_MARK(B, 11);
-        if (bwd_sweep()) break;
+        if (bwd_sweep()) {
+          if (part == sched::kPartBackward) {  // (a return from inside the loop, like the one below: see there)
+#if defined(DDP_TIMELINE) && !defined(DIRECT_EMULATE)
+            if (tl_ != nullptr && threadIdx.x == 0) { tl_[1] = __builtin_amdgcn_s_memrealtime(); tl_[3] = (unsigned long long)tl_split_; }
+#endif
+            return;
+          }
+          break;
+        }
         DDP_DBG_MARK(B, 12);
         note_failed_sweep();
         if (st.reg == 24 && st.bp_failed) st.bp_no_upd++;
@@ -3935,7 +3950,7 @@ struct Wave {
       }
     }
 #if defined(DDP_TIMELINE) && !defined(DIRECT_EMULATE)
-    if (tl_ != nullptr && threadIdx.x == 0) { tl_[1] = __builtin_amdgcn_s_memrealtime(); tl_[3] = (unsigned long long)tl_split_; }
+    if (part != sched::kPartSearch && tl_ != nullptr && threadIdx.x == 0) { tl_[1] = __builtin_amdgcn_s_memrealtime(); tl_[3] = (unsigned long long)tl_split_; }
 #endif
     DDP_DBG_MARK(B, 20);
     fwd_pass(helper);
@@ -4004,7 +4019,7 @@ struct Wave {
     }
   }
 
-  DDP_DEV void iterate(int n_iters, int helper = 0) {
+  DDP_DEV void iterate(int n_iters, int helper = 0, int part = sched::kPartWhole) {
 #pragma unroll 1
     for (int it = 0; it < n_iters; it++) {
       if (!helper) {
@@ -4019,8 +4034,8 @@ struct Wave {
       // the next sweep reads it (the first trip's iterate was released by the previous ticket's owner)
       if (!helper && it > 0 && bshare_slot() != nullptr) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
 #endif
-      iterate_once(helper);
-      if (helper) break;
+      iterate_once(helper, part);
+      if (helper || part == sched::kPartBackward) break;  // the iteration counts when its line search has run
       if (!st.done) {
         st.iter++;
         if (st.iter >= B.k.iter_max) st.done = 1;

@@ -97,6 +97,7 @@ struct Sched {
   int* done_epoch;    // [batch] chunks completed per trajectory
   int* err;           // [1] set to 1 when the spin limit is hit
   int chunk;
+  int half;           // 1: a ticket is half a trip of the outer loop (sched_ticket.h)
   int prio;           // raise the wave priority of chunks that had to wait for their predecessor
   int tail;           // rounds of help-only tickets behind the last epoch (next_work)
   // Yielding (DIRECT_FLAG_YIELD: another handle's launch is queued behind this one): a wave that is about to draw a ticket
@@ -126,8 +127,8 @@ struct Sched {
 // draws one waits for the trajectory's last chunk like any waiter - and so joins its open line searches (and shared
 // sweeps) - but never runs a chunk: -2 once that chunk is done.  Without them the waves leave a fixed-length launch as soon
 // as the tickets run out, and the last iterations of the slowest chains - the launch's tail - search alone on an emptying chip.
-__device__ __attribute__((noinline)) int next_work(Sched S, HelpSlot* slots, BwdShare* sweeps, const int32_t* idx, unsigned nb, unsigned total,
-                                                   unsigned total_help, int held, int* waited, int* help) {
+__device__ __attribute__((noinline)) int next_work(Sched S, HelpSlot* slots, BwdShare* sweeps, const int32_t* idx, sched::TicketPlan P, int held,
+                                                   int* waited, int* help) {
   unsigned t = (unsigned)held;
   if (held < 0) {
     unsigned tv = 0;
@@ -136,10 +137,9 @@ __device__ __attribute__((noinline)) int next_work(Sched S, HelpSlot* slots, Bwd
     *waited = 0;
   }
   *help = 0;
-  if (t >= total_help) return -1;
-  const int et = (int)(t / nb), bi = (int)(t - (unsigned)et * nb);
-  const int n_ep = (int)(total / nb);
-  const int e = et < n_ep ? et : n_ep;  // what the ticket waits for
+  if (t >= P.total_help) return -1;
+  const sched::Ticket tk = sched::ticket_decode(P, t);
+  const int e = tk.waits_for, bi = tk.slot;  // e: the units of the trajectory that must have been published
   const int b = idx ? __builtin_amdgcn_readfirstlane(idx[bi]) : bi;  // done_epoch / slots are indexed by the trajectory's own number
   int ready = (e == 0) ? 1 : 0, have = 0, wanted = 0;
   int spins = 0;
@@ -198,7 +198,7 @@ __device__ __attribute__((noinline)) int next_work(Sched S, HelpSlot* slots, Bwd
         S.dbg[5] = S.waves ? __hip_atomic_load(S.waves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
         S.dbg[6] = S.alive ? __hip_atomic_load(S.alive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : -1;
         S.dbg[8] = (int)((__builtin_amdgcn_s_memrealtime() - wait_t0) / 100000ull);  // the wait in milliseconds
-        S.dbg[9] = (int)nb; S.dbg[10] = (int)total; S.dbg[11] = spins;
+        S.dbg[9] = (int)P.nb; S.dbg[10] = (int)P.total; S.dbg[11] = spins;
 #if defined(DDP_SCHED_DEBUG)
         if (S.mark != nullptr) {  // where the launch's waves are: a histogram of their marks, and three of the waves inside a chunk
           int n_in = 0;
@@ -220,7 +220,7 @@ __device__ __attribute__((noinline)) int next_work(Sched S, HelpSlot* slots, Bwd
     }
     return -3 - b;
   }
-  if (have >= kDoneBit || t >= total) return -2;
+  if (have >= kDoneBit || !tk.runs) return -2;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   return (int)t;
 }
@@ -230,10 +230,8 @@ __global__ __launch_bounds__(64, (RPL > 7 ? DDP_WAVES_WIDER : (RPL > 4 ? DDP_WAV
   __shared__ WaveLds<Cmp, St, RPL> lds;
   Wave<Cmp, St, RPL, SHARE> W(B, lds, 0);
   W.init_tables();
-  const unsigned nb = (unsigned)B.B;
-  const unsigned n_epochs = (unsigned)((n_iters + S.chunk - 1) / S.chunk);
-  const unsigned total = nb * n_epochs;
-  const unsigned total_help = B.help ? total + nb * (unsigned)S.tail : total;
+  const sched::TicketPlan P = sched::ticket_plan(B.B, n_iters, S.chunk, S.half, B.help ? S.tail : 0);
+  const unsigned nb = P.nb;
   DDP_MARK("Z_0");
   int held = -1, waited = 0;
 #pragma unroll 1
@@ -259,14 +257,14 @@ __global__ __launch_bounds__(64, (RPL > 7 ? DDP_WAVES_WIDER : (RPL > 4 ? DDP_WAV
     // chunk it has just finished
     if (S.prio) __builtin_amdgcn_s_setprio(0);
 #endif
-    const int t = __builtin_amdgcn_readfirstlane(next_work(S, B.help, SHARE ? B.bshare : nullptr, B.idx, nb, total, total_help, held, &waited, &help_v));
+    const int t = __builtin_amdgcn_readfirstlane(next_work(S, B.help, SHARE ? B.bshare : nullptr, B.idx, P, held, &waited, &help_v));
     const int help = __builtin_amdgcn_readfirstlane(help_v);
     DDP_MARK("X_G");
     held = -1;
     if (t == -1) break;
     if (t == -2) continue;
     if (t <= -3) {  // timed out: retire the trajectory so that its later tickets are skipped at once
-      if (threadIdx.x == 0) __hip_atomic_fetch_max(&S.done_epoch[-3 - t], kDoneBit | (int)n_epochs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (threadIdx.x == 0) __hip_atomic_fetch_max(&S.done_epoch[-3 - t], kDoneBit | (int)P.units, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       continue;
     }
     const int e = __builtin_amdgcn_readfirstlane((int)((unsigned)t / nb));
@@ -280,22 +278,23 @@ __global__ __launch_bounds__(64, (RPL > 7 ? DDP_WAVES_WIDER : (RPL > 4 ? DDP_WAV
       else __builtin_amdgcn_s_setprio(0);
     }
     // One call site of Wave::iterate for both kinds of work (the sweeps are inlined into it).
-    int run = 1, n = 1;
+    int run = 1, n = 1, part = sched::kPartWhole;
     if (help) {
       held = t;  // the ticket stays in hand
       W.N = __builtin_amdgcn_readfirstlane(B.n_seg[b]);
     } else {
       W.load_state();
       run = __builtin_amdgcn_readfirstlane(lds.st.done) ? 0 : 1;
-      const int left = n_iters - e * S.chunk;
-      n = left < S.chunk ? left : S.chunk;
+      const sched::Work wk = sched::unit_work(P, e);
+      n = wk.n;
+      part = wk.part;
     }
 #if defined(DDP_SCHED_DEBUG)
     if (!help && threadIdx.x == 0) __hip_atomic_fetch_add(&S.dbg[13], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     DDP_DBG_MARK(B, help ? 6 : 5);
     if (B.mark != nullptr && threadIdx.x == 0) B.mark[gridDim.x + blockIdx.x] = b;  // the trajectory
 #endif
-    if (run) W.iterate(n, help);
+    if (run) W.iterate(n, help, part);
     DDP_DBG_MARK(B, 40);
 #if defined(DDP_SCHED_DEBUG)
     if (!help && threadIdx.x == 0) __hip_atomic_fetch_add(&S.dbg[13], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -313,7 +312,7 @@ __global__ __launch_bounds__(64, (RPL > 7 ? DDP_WAVES_WIDER : (RPL > 4 ? DDP_WAV
       // max, not store: done_epoch only ever grows, and a trajectory that a timed-out waiter has retired
       // (kDoneBit | n_epochs, below) stays retired when its straggling chunk completes afterwards
       if (threadIdx.x == 0) {
-        __hip_atomic_fetch_max(&S.done_epoch[b], (e + 1) | fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_max(&S.done_epoch[b], sched::published_after(e) | fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #if defined(DDP_SCHED_DEBUG)
         __hip_atomic_fetch_add(&S.dbg[27], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // left it
 #endif
@@ -575,6 +574,7 @@ struct direct_ddp_handle_s {
   int sched_slots = 0;   // resident one-wave workgroups of k_iterate_dyn on this device (the handle's own class)
   int slots_cap = 0;     // DIRECT_DDP_SLOTS: fewer persistent waves than fit (experiments)
   int sched_chunk = 1;   // outer-loop trips per ticket (DIRECT_DDP_CHUNK at create time; experiments)
+  int sched_half = -1;   // a ticket is HALF a trip (backward sweep | line search; sched_ticket.h): -1 auto, DIRECT_DDP_HALF=0|1 forces
   int pair_trials = -1;  // two line-search steps per forward sweep from the second attempt on: -1 auto, DIRECT_DDP_PAIR=0|1 forces
   int sched_prio = 1;    // chunks that had to wait for their predecessor run at raised wave priority (DIRECT_DDP_PRIO=0: off)
   int sched_tail = 8;    // rounds of help-only tickets behind the last epoch (DIRECT_DDP_TAIL=0: none; next_work)
@@ -785,7 +785,7 @@ static void launch_iterate_t(direct_ddp_handle_t h, int n, int mode) {
     const bool is_big = biggest < 0 || c.cnt > classes[biggest].cnt;
     if (is_big) {
       biggest = (int)ci;
-      li.pair_trials = Bt.k.pair_trials; li.resident_waves = slots; li.dynamic = 0; li.shared_search = 0; li.single_steps = 0;
+      li.pair_trials = Bt.k.pair_trials; li.resident_waves = slots; li.dynamic = 0; li.shared_search = 0; li.single_steps = 0; li.half_tickets = 0;
       li.shared_sweep = 0;
     }
     // backward sweeps shared with helpers wherever the line search is; the forced split needs no helper (any launch form)
@@ -821,7 +821,10 @@ static void launch_iterate_t(direct_ddp_handle_t h, int n, int mode) {
       S.ticket = (unsigned*)(h->tickets + (ci < 16 ? ci : 15));
       S.err = h->sched + 1;
       S.done_epoch = h->sched + 2;
-      S.chunk = h->sched_chunk;
+      // Half-trip tickets (sched_ticket.h): scheduling only.  Auto = whole trips: measured no faster in any regime
+      // 
+      S.half = h->sched_half > 0 ? 1 : 0;
+      S.chunk = S.half ? 1 : h->sched_chunk;
       S.prio = h->sched_prio;
       S.tail = help ? h->sched_tail : 0;
       S.dbg = h->sched_dbg;
@@ -852,12 +855,12 @@ static void launch_iterate_t(direct_ddp_handle_t h, int n, int mode) {
         // B = 256 19.1 -> 18.8 ms); from a third of the resident waves on, the waiters' help no longer covers the sharing
         // instantiation's slower fused path (B = 1024 22.3 -> 23.6 ms, 3072 29.5 -> 32.0, 4096 35.1 -> 37.8; same-box A/B):
         // auto = batches up to an eighth of the resident waves, like the single-step line search
-        if (sweep_ok && h->bshare_mode != 0 && h->bshare_mode != 2 && h->sched_chunk == 1 && (h->bshare_mode > 0 || 8 * c.cnt <= slots)) {
+        if (sweep_ok && h->bshare_mode != 0 && h->bshare_mode != 2 && S.chunk == 1 && (h->bshare_mode > 0 || 8 * c.cnt <= slots)) {
           Bt.bshare = h->bshare; Bt.bflag = h->bflag; Bt.brec = h->brec; Bt.bforce = 0; Bt.bvisits = h->visits + 2;
           if (is_big) li.shared_sweep = 1;
         }
       }
-      if (is_big) li.dynamic = 1;
+      if (is_big) { li.dynamic = 1; li.half_tickets = S.half; }
       if (Bt.bshare) {
         publish(Bt);
         switch (c.rpl) {  // sweep_ok: row-slot classes 2 .. 4
@@ -1178,6 +1181,7 @@ direct_status_t direct_ddp_create(const direct_ddp_config_t* cfg, direct_ddp_han
   A(&h->tickets, 16 * sizeof(int));
   A(&h->order, B * sizeof(int32_t)); A(&h->cls_dev, B * sizeof(int32_t));
   if (const char* ev = getenv("DIRECT_DDP_CHUNK")) h->sched_chunk = atoi(ev) > 0 ? atoi(ev) : 1;
+  if (const char* ev = getenv("DIRECT_DDP_HALF")) h->sched_half = atoi(ev) > 0 ? 1 : 0;
   if (const char* ev = getenv("DIRECT_DDP_PRIO")) h->sched_prio = atoi(ev);
   if (const char* ev = getenv("DIRECT_DDP_TAIL")) h->sched_tail = std::max(0, std::min(atoi(ev), 64));
   if (const char* ev = getenv("DIRECT_DDP_PAIR")) h->pair_trials = atoi(ev);

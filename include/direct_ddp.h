@@ -491,6 +491,9 @@ typedef struct {
   uint64_t bwd_knot_visits; /* backward-sweep knots executed by the launch (all trajectories, retries included) */
   uint64_t fwd_knot_visits; /* forward trial-knots executed (every trial of every line search, helpers' included;
                                a trial cut short by the fraction-to-boundary rule counts the knots it reached) */
+  int32_t half_tickets;     /* 1: the ticket scheduler handed out half trips of the outer loop (the backward sweep with its
+                               retries | the line search with the exit rules) instead of whole ones (DIRECT_DDP_HALF=1) */
+  int32_t reserved;
 } direct_ddp_launch_info_t;
 direct_status_t direct_ddp_last_launch_info(direct_ddp_handle_t h, direct_ddp_launch_info_t* info);
 /* Work counters of the last hot-kernel launch (observability only): out4[0] backward-sweep knots, out4[1] forward

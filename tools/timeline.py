@@ -24,8 +24,9 @@ lib.direct_ddp_debug_timeline.argtypes = [C.c_void_p, C.c_void_p]
 assert lib.direct_ddp_debug_timeline(s.h, tl.ctypes.data) == 0
 tl = tl[:, :IT].astype(np.int64)
 t0 = tl[:, :, 0].min()
-st, mid, en, sp = (tl[:, :, 0] - t0) / 100.0, (tl[:, :, 1] - t0) / 100.0, (tl[:, :, 2] - t0) / 100.0, tl[:, :, 3]  # us
-dur = en - st
+st, mid, en, sp = (tl[:, :, 0] - t0) / 100.0, (tl[:, :, 1] - t0) / 100.0, (tl[:, :, 2] - t0) / 100.0, tl[:, :, 3] & 0xffffffff  # us
+hgap = (tl[:, :, 3] >> 32) / 100.0  # half-trip tickets (DIRECT_DDP_HALF=1): the wait between an iteration's two tickets; else 0
+dur = en - st - hgap
 busy = dur.sum(1)
 span = en.max()
 slots = li["resident_waves"]
@@ -36,12 +37,13 @@ out = {
     "helper_front_knots": li.get("helper_front_knots", 0), "bwd_knot_visits": li["bwd_knot_visits"],
     "work_bound_us": float(busy.sum() / slots), "busy_us_q50_q90_max": [float(v) for v in np.quantile(busy, [0.5, 0.9, 1.0])],
     "iteration_us_mean_q50_q90_max": [float(dur.mean())] + [float(v) for v in np.quantile(dur, [0.5, 0.9, 1.0])],
-    "bwd_us_mean": float((mid - st).mean()), "fwd_us_mean": float((en - mid).mean()),
+    "half_tickets": li.get("half_tickets", 0), "idle_between_halves_us_mean_per_trajectory": float(hgap.sum(1).mean()),
+    "bwd_us_mean": float((mid - st).mean()), "fwd_us_mean": float((en - mid - hgap).mean()),
     "first_start_us_q50_q90_max": [float(v) for v in np.quantile(st[:, 0], [0.5, 0.9, 1.0])],
     "idle_between_iterations_us_mean_per_trajectory": float(gaps.sum(1).mean()),
     "split_knot_share": float(sp.sum() / max(li["bwd_knot_visits"], 1)),
     "last_finishers": [dict(traj=int(i), finish_us=float(en[i, -1]), busy_us=float(busy[i]), first_start_us=float(st[i, 0]),
-                            idle_us=float(gaps[i].sum()), bwd_us=float((mid[i] - st[i]).sum()), split_knots=int(sp[i].sum())) for i in last],
+                            idle_us=float(gaps[i].sum()), idle_halves_us=float(hgap[i].sum()), bwd_us=float((mid[i] - st[i]).sum()), split_knots=int(sp[i].sum())) for i in last],
     "corr_consecutive_iteration_durations": float(np.corrcoef(dur[:, :-1].ravel(), dur[:, 1:].ravel())[0, 1]),
     "corr_first_half_second_half_busy": float(np.corrcoef(dur[:, :IT // 2].sum(1), dur[:, IT // 2:].sum(1))[0, 1]),
 }
