@@ -240,28 +240,43 @@ class ClusterGenerator:
         -> dict(path_xyz [B][path_capacity][3] int32, path_len, path_cost, rtn, stats)"""
         starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
         goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
-        assert starts.shape == goals.shape and mem in ("host", "device")
+        assert starts.shape == goals.shape
         B, cap = starts.shape[0], int(path_capacity)
+        out, mem_abi, ptr = self._path_outputs(mem, B, B, cap, False, want_dist)
+        _check(_lib().direct_cluster_grid_path_batch(self.h, B, starts.ctypes.data, goals.ctypes.data, cap, int(max_rounds), mem_abi,
+                                                     *[ptr(k) for k in ("path_xyz", "path_len", "path_cost", "dist", "stats", "rtn")]))
+        return out if mem == "device" else self._path_rows(out, cap)
+
+    def _path_outputs(self, mem, n, n_field, cap, clear, want_dist):
+        """The zeroed output set of a grid-path call with n paths on n_field fields (stats and dist are per field; path_d2 and
+        path_min_d2 come with `clear`): NumPy arrays and a dist entry (None unless wanted) for mem="host", tensors in the C-ABI's
+        layout for mem="device".  -> (dict, the C-ABI's memory kind, key -> address or None)"""
+        assert mem in ("host", "device")
         if mem == "device":
             import torch
             assert not want_dist
             z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
-            out = dict(path_xyz=z((B, cap, 3), torch.int32), path_len=z(B, torch.int32), path_cost=z(B, torch.float64),
-                       stats=z((B, 2), torch.int32), rtn=z(B, torch.int32))
+            i32, f64 = torch.int32, torch.float64
+        else:
+            z, i32, f64 = np.zeros, np.int32, np.float64
+        out = dict(path_xyz=z((n, cap, 3), i32), path_len=z(n, i32), path_cost=z(n, f64), stats=z((n_field, 2), i32), rtn=z(n, i32))
+        if clear:
+            out.update(path_d2=z((n, cap), i32), path_min_d2=z(n, i32))
+        if mem == "device":
             torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
-            _check(_lib().direct_cluster_grid_path_batch(self.h, B, starts.ctypes.data, goals.ctypes.data, cap, int(max_rounds),
-                                                         abi.MEM_DEVICE, out["path_xyz"].data_ptr(), out["path_len"].data_ptr(),
-                                                         out["path_cost"].data_ptr(), None, out["stats"].data_ptr(), out["rtn"].data_ptr()))
-            return out
-        xyz = np.zeros((B, cap, 3), np.int32)
-        n, rtn, stats = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros((B, 2), np.int32)
-        cost = np.zeros(B, np.float64)
-        dist = np.zeros((B, int(np.prod(self.dims))), np.float64) if want_dist else None
-        _check(_lib().direct_cluster_grid_path_batch(self.h, B, starts.ctypes.data, goals.ctypes.data, cap, int(max_rounds),
-                                                     abi.MEM_HOST, xyz.ctypes.data, n.ctypes.data, cost.ctypes.data,
-                                                     dist.ctypes.data if want_dist else None, stats.ctypes.data, rtn.ctypes.data))
-        return dict(paths=[xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)], path_len=n, path_cost=cost, rtn=rtn, stats=stats,
-                    dist=dist)
+            return out, abi.MEM_DEVICE, lambda k: out[k].data_ptr() if k in out else None
+        out["dist"] = np.zeros((n_field, int(np.prod(self.dims))), np.float64) if want_dist else None
+        return out, abi.MEM_HOST, lambda k: None if out.get(k) is None else out[k].ctypes.data
+
+    @staticmethod
+    def _path_rows(out, cap):
+        """Host outputs as the callers get them: path_xyz becomes paths, a list of each row's filled prefix, and so does path_d2."""
+        n = [min(int(v), cap) for v in out["path_len"]]
+        xyz = out.pop("path_xyz")
+        out["paths"] = [xyz[b, :n[b]].copy() for b in range(len(n))]
+        if "path_d2" in out:
+            out["path_d2"] = [out["path_d2"][b, :n[b]].copy() for b in range(len(n))]
+        return out
 
     def grid_paths_clear(self, starts, goals, min_d2=0, penalty=None, path_capacity=4096, max_rounds=0, want_dist=False, mem="host"):
         """grid_paths on the resident distance field (direct_cluster_grid_path_clear_batch; build_distance_field must have run since
@@ -272,32 +287,15 @@ class ClusterGenerator:
         voxel, and path_min_d2 [B], the minimum over the path without its start (DIST_NONE for a path of one voxel or none)."""
         starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
         goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
-        assert starts.shape == goals.shape and mem in ("host", "device")
+        assert starts.shape == goals.shape
         B, cap = starts.shape[0], int(path_capacity)
         pen = None if penalty is None else np.ascontiguousarray(penalty, np.float64).reshape(-1)
         par = GridPathClearIn(batch=B, path_capacity=cap, max_rounds=int(max_rounds), starts=starts.ctypes.data, goals=goals.ctypes.data,
                               min_d2=int(min_d2), n_penalty=0 if pen is None else len(pen), penalty=None if pen is None else pen.ctypes.data)
-        if mem == "device":
-            import torch
-            assert not want_dist
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
-            out = dict(path_xyz=z((B, cap, 3), torch.int32), path_len=z(B, torch.int32), path_cost=z(B, torch.float64),
-                       stats=z((B, 2), torch.int32), rtn=z(B, torch.int32), path_d2=z((B, cap), torch.int32), path_min_d2=z(B, torch.int32))
-            torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
-            par.mem = abi.MEM_DEVICE
-            o = GridPathClearOut(*[out[k].data_ptr() if k in out else None for k in abi.GRID_PATH_CLEAR_OUTPUTS])
-            _check(_lib().direct_cluster_grid_path_clear_batch(self.h, C.addressof(par), C.addressof(o)))
-            return out
-        out = dict(path_xyz=np.zeros((B, cap, 3), np.int32), path_len=np.zeros(B, np.int32), path_cost=np.zeros(B, np.float64),
-                   dist=np.zeros((B, int(np.prod(self.dims))), np.float64) if want_dist else None, stats=np.zeros((B, 2), np.int32),
-                   rtn=np.zeros(B, np.int32), path_d2=np.zeros((B, cap), np.int32), path_min_d2=np.zeros(B, np.int32))
-        par.mem = abi.MEM_HOST
-        o = GridPathClearOut(*[None if out[k] is None else out[k].ctypes.data for k in abi.GRID_PATH_CLEAR_OUTPUTS])
+        out, par.mem, ptr = self._path_outputs(mem, B, B, cap, True, want_dist)
+        o = GridPathClearOut(*[ptr(k) for k in abi.GRID_PATH_CLEAR_OUTPUTS])
         _check(_lib().direct_cluster_grid_path_clear_batch(self.h, C.addressof(par), C.addressof(o)))
-        n, xyz, d2 = out["path_len"], out.pop("path_xyz"), out["path_d2"]
-        out["paths"] = [xyz[b, :min(int(n[b]), cap)].copy() for b in range(B)]
-        out["path_d2"] = [d2[b, :min(int(n[b]), cap)].copy() for b in range(B)]
-        return out
+        return out if mem == "device" else self._path_rows(out, cap)
 
     def grid_paths_fan(self, sources, goals, goal_src=None, min_d2=0, penalty=None, path_capacity=4096, max_rounds=0, want_dist=False,
                        mem="host"):
@@ -310,40 +308,17 @@ class ClusterGenerator:
         sources = np.ascontiguousarray(sources, np.int32).reshape(-1, 3)
         goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
         gs = None if goal_src is None else np.ascontiguousarray(goal_src, np.int32).reshape(-1)
-        assert mem in ("host", "device") and (gs is None or len(gs) == len(goals))
+        assert gs is None or len(gs) == len(goals)
         S, n, cap = sources.shape[0], goals.shape[0], int(path_capacity)
         pen = None if penalty is None or len(penalty) == 0 else np.ascontiguousarray(penalty, np.float64).reshape(-1)
         clear = not (int(min_d2) <= 1 and pen is None)
         par = GridPathFanIn(n_src=S, n_goal=n, path_capacity=cap, max_rounds=int(max_rounds), sources=sources.ctypes.data,
                             goals=goals.ctypes.data, goal_src=None if gs is None else gs.ctypes.data, min_d2=int(min_d2),
                             n_penalty=0 if pen is None else len(pen), penalty=None if pen is None else pen.ctypes.data)
-        if mem == "device":
-            import torch
-            assert not want_dist
-            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda:%d" % self.device)
-            out = dict(path_xyz=z((n, cap, 3), torch.int32), path_len=z(n, torch.int32), path_cost=z(n, torch.float64),
-                       stats=z((S, 2), torch.int32), rtn=z(n, torch.int32))
-            if clear:
-                out.update(path_d2=z((n, cap), torch.int32), path_min_d2=z(n, torch.int32))
-            torch.cuda.current_stream(out["rtn"].device).synchronize()  # the handle's stream is not torch's
-            par.mem = abi.MEM_DEVICE
-            o = GridPathFanOut(*[out[k].data_ptr() if k in out else None for k in abi.GRID_PATH_FAN_OUTPUTS])
-            _check(_lib().direct_cluster_grid_path_fan_batch(self.h, C.addressof(par), C.addressof(o)))
-            return out
-        out = dict(path_xyz=np.zeros((n, cap, 3), np.int32), path_len=np.zeros(n, np.int32), path_cost=np.zeros(n, np.float64),
-                   dist=np.zeros((S, int(np.prod(self.dims))), np.float64) if want_dist else None, stats=np.zeros((S, 2), np.int32),
-                   rtn=np.zeros(n, np.int32))
-        if clear:
-            out.update(path_d2=np.zeros((n, cap), np.int32), path_min_d2=np.zeros(n, np.int32))
-        par.mem = abi.MEM_HOST
-        o = GridPathFanOut(*[None if out.get(k) is None else out[k].ctypes.data for k in abi.GRID_PATH_FAN_OUTPUTS])
+        out, par.mem, ptr = self._path_outputs(mem, n, S, cap, clear, want_dist)
+        o = GridPathFanOut(*[ptr(k) for k in abi.GRID_PATH_FAN_OUTPUTS])
         _check(_lib().direct_cluster_grid_path_fan_batch(self.h, C.addressof(par), C.addressof(o)))
-        ln, xyz = out["path_len"], out.pop("path_xyz")
-        out["paths"] = [xyz[b, :min(int(ln[b]), cap)].copy() for b in range(n)]
-        if clear:
-            d2 = out["path_d2"]
-            out["path_d2"] = [d2[b, :min(int(ln[b]), cap)].copy() for b in range(n)]
-        return out
+        return out if mem == "device" else self._path_rows(out, cap)
 
     def check_plans(self, n_seg, T, map_lower, resolution, bez=None, poly=None, depth=8, margin=0.0, t_from=None, outside_blocks=False, count=False):
         """Solved plans against the map the handle holds now (direct_cluster_plan_check_batch): for every plan whether the curve

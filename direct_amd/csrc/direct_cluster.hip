@@ -1072,23 +1072,20 @@ hipError_t path_workspace(direct_cluster_handle_t h) {
   return hipSuccess;
 }
 
-template <bool Clear>
-hipError_t fan_rounds(direct_cluster_handle_t h, const PathClearDev& C, const FanDev& F, long long lim, int* rounds_done) {
-  // the rounds of direct_cluster_grid_path_batch over (tiles, sources): separate launches, enqueued eight at a time, then ONE
-  // read-back; k_fan_bound goes in front of every round or of every batch of rounds (fan_bound_every)
-  const PathDev& P = h->P;
-  std::vector<int> pending((size_t)F.n_src);
+// The rounds of the three grid-path calls.  Rounds are separate launches, enqueued blindly gp::kFanRoundsPerCheck at a time (a
+// workgroup whose tile is not active returns at once); then ONE read-back of the first n_slots "a tile was woken in round r"
+// words says whether any slot goes on.  enqueue(r) launches round r.  *rounds_done counts the rounds enqueued, also on an error.
+template <class Enqueue>
+hipError_t path_rounds(direct_cluster_handle_t h, size_t n_slots, long long lim, int* rounds_done, Enqueue enqueue) {
+  std::vector<int> pending(n_slots);
   int done = 0;
   while (done < lim) {
     const int n = (int)std::min<long long>(gp::kFanRoundsPerCheck, lim - done);
-    for (int r = 0; r < n; r++) {
-      if (r % h->fan_bound_every == 0) hipLaunchKernelGGL(k_fan_bound<Clear>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
-      hipLaunchKernelGGL(k_fan_relax<Clear>, dim3(P.ntiles, F.n_src), dim3(256), 0, h->stream, P, C, (const double*)F.bound, done + r);
-    }
+    for (int r = 0; r < n; r++) enqueue(done + r);
     hipError_t e = hipGetLastError();
     done += n;
     *rounds_done = done;
-    if (e == hipSuccess) e = hipMemcpyAsync(pending.data(), P.pending, pending.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(pending.data(), h->P.pending, n_slots * sizeof(int), hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) return e;
     bool live = false;
@@ -1096,6 +1093,58 @@ hipError_t fan_rounds(direct_cluster_handle_t h, const PathClearDev& C, const Fa
     if (!live) break;
   }
   return hipSuccess;
+}
+
+// The clearance parameters of grid_path_clear_batch and grid_path_fan_batch, in two steps, because what the arguments alone
+// decide is refused before what the handle holds: each gives the refusal's text, or null.
+const char* clear_args_refusal(int32_t min_d2, int32_t n_penalty, const double* penalty) {
+  if (min_d2 < 0) return "min_d2 must not be negative";
+  if (n_penalty < 0 || n_penalty > gp::kMaxPenalty) return "n_penalty outside [0, 65536]";
+  if (n_penalty > 0 && !penalty) return "a NULL penalty requires n_penalty == 0";
+  for (int i = 0; i < n_penalty; i++)
+    if (!std::isfinite(penalty[i]) || !(penalty[i] >= 0.0)) return "penalty entries must be finite and not negative";
+  return nullptr;
+}
+const char* clear_field_refusal(direct_cluster_handle_t h, int32_t min_d2, int32_t n_penalty) {
+  if (!h->dist_valid) return "no valid distance field: call direct_cluster_distance_field after the map changes";
+  // a stored cap2 means "at least cap2": neither the floor nor the table may tell values at or above it apart (an uncapped
+  // field has cap2 = DIRECT_DIST_NONE, which refuses nothing)
+  if (min_d2 > h->dist_cap2 || n_penalty > h->dist_cap2) return "min_d2 or n_penalty above the cap2 the distance field was built with";
+  return nullptr;
+}
+
+// The penalty table on the device: path_pen, allocated by the first call with a table, and the upload of this call's entries
+direct_status_t upload_penalty(direct_cluster_handle_t h, int32_t n_penalty, const double* penalty, const char* who) {
+  if (n_penalty <= 0) return DIRECT_OK;
+  if (!h->path_pen) {
+    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->path_pen, (size_t)gp::kMaxPenalty * sizeof(double))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string(who) + ": table allocation: " + hipGetErrorString(ae));
+  }
+  CHIP_TRY(hipMemcpyAsync(h->path_pen, penalty, (size_t)n_penalty * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return DIRECT_OK;
+}
+
+PathClearDev clear_dev(direct_cluster_handle_t h, int32_t min_d2, int32_t n_penalty) {
+  PathClearDev C = {};
+  C.d2 = h->dist[0];
+  C.pen = n_penalty > 0 ? h->path_pen : nullptr;
+  C.n_pen = n_penalty; C.min_d2 = min_d2;
+  return C;
+}
+
+// PathDev::ends of n slots on the host (the caller keeps it alive until its copy has drained)
+std::vector<int> pack_ends(size_t n, const int32_t* starts, const int32_t* goals) {
+  std::vector<int> ends(n * 6);
+  for (size_t b = 0; b < n; b++)
+    for (int a = 0; a < 3; a++) { ends[6 * b + a] = starts[3 * b + a]; ends[6 * b + 3 + a] = goals[3 * b + a]; }
+  return ends;
+}
+
+// the fields of n slots to the caller's `dist` (null: nothing), unless e already holds an error
+hipError_t download_fields(direct_cluster_handle_t h, double* dist, size_t n, int32_t mem, hipError_t e) {
+  if (e != hipSuccess || !dist) return e;
+  return hipMemcpyAsync(dist, h->P.field, n * (size_t)h->P.G * sizeof(double),
+                        mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
 }
 }  // namespace
 
@@ -1491,39 +1540,22 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
   for (int i = 0; i < 5; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
   CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
   P.cap = (int)cap;
-  std::vector<int> ends(nb * 6);
-  for (size_t b = 0; b < nb; b++)
-    for (int a = 0; a < 3; a++) { ends[6 * b + a] = starts[3 * b + a]; ends[6 * b + 3 + a] = goals[3 * b + a]; }
+  const std::vector<int> ends = pack_ends(nb, starts, goals);
   CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hs::start(h->ev, h->stream));
   hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
   CHIP_TRY(hipGetLastError());
-  // Rounds are separate launches, enqueued blindly kRoundsPerCheck at a time (a workgroup whose tile is not active returns at
-  // once); then ONE read-back of the per-query "a tile was woken in round r" words says whether any query goes on.
-  constexpr int kRoundsPerCheck = 8;
   const long long lim = max_rounds > 0 ? (long long)max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
-  std::vector<int> pending(nb);
   int done = 0;
-  while (done < lim) {
-    const int n = (int)std::min<long long>(kRoundsPerCheck, lim - done);
-    for (int r = 0; r < n; r++) hipLaunchKernelGGL(k_path_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, done + r);
-    CHIP_TRY(hipGetLastError());
-    done += n;
-    CHIP_TRY(hipMemcpyAsync(pending.data(), P.pending, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CHIP_TRY(hipStreamSynchronize(h->stream));
-    bool live = false;
-    for (int v : pending) live |= v == done;
-    if (!live) break;
-  }
+  const hipError_t re = path_rounds(h, nb, lim, &done, [&](int r) {
+    hipLaunchKernelGGL(k_path_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, r);
+  });
+  if (re != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: rounds: ") + hipGetErrorString(re));
   hipLaunchKernelGGL(k_path_trace, dim3(batch), dim3(64), 0, h->stream, P, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
                      (int32_t*)dev[3], (int32_t*)dev[4]);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::stage_download(st, h->stream, e);
-  if (e == hipSuccess && dist)
-    e = hipMemcpyAsync(dist, P.field, nb * (size_t)P.G * sizeof(double),
-                       mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
-  e = hs::drain(h->stream, e);
+  e = hs::drain(h->stream, download_fields(h, dist, nb, mem, hs::stage_download(st, h->stream, e)));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
@@ -1748,30 +1780,16 @@ direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, 
   if (in->batch <= 0) return cfail(DIRECT_ERR_INVALID, "batch must be positive");
   if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
   if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
-  if (in->n_penalty < 0 || in->n_penalty > gp::kMaxPenalty) return cfail(DIRECT_ERR_INVALID, "n_penalty outside [0, 65536]");
-  if (in->n_penalty > 0 && !in->penalty) return cfail(DIRECT_ERR_INVALID, "a NULL penalty requires n_penalty == 0");
-  for (int i = 0; i < in->n_penalty; i++)
-    if (!std::isfinite(in->penalty[i]) || !(in->penalty[i] >= 0.0)) return cfail(DIRECT_ERR_INVALID, "penalty entries must be finite and not negative");
+  if (const char* why = clear_args_refusal(in->min_d2, in->n_penalty, in->penalty)) return cfail(DIRECT_ERR_INVALID, why);
   if (in->batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
   if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
-  // a stored cap2 means "at least cap2": neither the floor nor the table may tell values at or above it apart (an uncapped
-  // field has cap2 = DIRECT_DIST_NONE, which refuses nothing)
-  if (in->min_d2 > h->dist_cap2 || in->n_penalty > h->dist_cap2)
-    return cfail(DIRECT_ERR_INVALID, "min_d2 or n_penalty above the cap2 the distance field was built with");
+  if (const char* why = clear_field_refusal(h, in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
     return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: workspace allocation: ") + hipGetErrorString(ae));
-  if (in->n_penalty > 0 && !h->path_pen) {
-    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->path_pen, (size_t)gp::kMaxPenalty * sizeof(double))});
-    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: table allocation: ") + hipGetErrorString(ae));
-  }
+  if (const direct_status_t us = upload_penalty(h, in->n_penalty, in->penalty, "grid_path_clear_batch"); us != DIRECT_OK) return us;
   PathDev& P = h->P;
-  PathClearDev C = {};
-  C.d2 = h->dist[0];
-  C.pen = in->n_penalty > 0 ? h->path_pen : nullptr;
-  C.n_pen = in->n_penalty; C.min_d2 = in->min_d2;
+  PathClearDev C = clear_dev(h, in->min_d2, in->n_penalty);
   // one block for the two read-back rings (scratch slices, needed whatever `mem` is) and the staging of host outputs
   const int batch = in->batch;
   const size_t nb = (size_t)batch, cap = (size_t)in->path_capacity;
@@ -1785,40 +1803,22 @@ direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, 
   for (int i = 0; i < 7; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
   CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
   P.cap = (int)cap;
-  std::vector<int> ends(nb * 6);
-  for (size_t b = 0; b < nb; b++)
-    for (int a = 0; a < 3; a++) { ends[6 * b + a] = in->starts[3 * b + a]; ends[6 * b + 3 + a] = in->goals[3 * b + a]; }
+  const std::vector<int> ends = pack_ends(nb, in->starts, in->goals);
   CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (in->n_penalty > 0)
-    CHIP_TRY(hipMemcpyAsync(h->path_pen, in->penalty, (size_t)in->n_penalty * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hs::start(h->ev, h->stream));
   hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
   CHIP_TRY(hipGetLastError());
-  // the rounds of direct_cluster_grid_path_batch: separate launches, enqueued eight at a time, then ONE read-back
-  constexpr int kRoundsPerCheck = 8;
   const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
-  std::vector<int> pending(nb);
   int done = 0;
-  while (done < lim) {
-    const int n = (int)std::min<long long>(kRoundsPerCheck, lim - done);
-    for (int r = 0; r < n; r++) hipLaunchKernelGGL(k_path_clear_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, C, done + r);
-    CHIP_TRY(hipGetLastError());
-    done += n;
-    CHIP_TRY(hipMemcpyAsync(pending.data(), P.pending, nb * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    CHIP_TRY(hipStreamSynchronize(h->stream));
-    bool live = false;
-    for (int v : pending) live |= v == done;
-    if (!live) break;
-  }
+  const hipError_t re = path_rounds(h, nb, lim, &done, [&](int r) {
+    hipLaunchKernelGGL(k_path_clear_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, C, r);
+  });
+  if (re != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: rounds: ") + hipGetErrorString(re));
   hipLaunchKernelGGL(k_path_clear_trace, dim3(batch), dim3(64), 0, h->stream, P, C, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
                      (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (int32_t*)dev[6]);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::stage_download(st, h->stream, e);
-  if (e == hipSuccess && out->dist)
-    e = hipMemcpyAsync(out->dist, P.field, nb * (size_t)P.G * sizeof(double),
-                       in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
-  e = hs::drain(h->stream, e);
+  e = hs::drain(h->stream, download_fields(h, out->dist, nb, in->mem, hs::stage_download(st, h->stream, e)));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
@@ -1831,11 +1831,7 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   if (in->n_goal < 1) return cfail(DIRECT_ERR_INVALID, "n_goal must be positive");
   if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
   if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
-  if (in->n_penalty < 0 || in->n_penalty > gp::kMaxPenalty) return cfail(DIRECT_ERR_INVALID, "n_penalty outside [0, 65536]");
-  if (in->n_penalty > 0 && !in->penalty) return cfail(DIRECT_ERR_INVALID, "a NULL penalty requires n_penalty == 0");
-  for (int i = 0; i < in->n_penalty; i++)
-    if (!std::isfinite(in->penalty[i]) || !(in->penalty[i] >= 0.0)) return cfail(DIRECT_ERR_INVALID, "penalty entries must be finite and not negative");
+  if (const char* why = clear_args_refusal(in->min_d2, in->n_penalty, in->penalty)) return cfail(DIRECT_ERR_INVALID, why);
   if (!in->goal_src && in->n_src != 1) return cfail(DIRECT_ERR_INVALID, "a NULL goal_src requires n_src == 1");
   if (in->goal_src)
     for (int j = 0; j < in->n_goal; j++)
@@ -1845,28 +1841,17 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
     return cfail(DIRECT_ERR_INVALID, "path_d2 and path_min_d2 must be NULL in neutral mode (min_d2 <= 1, n_penalty == 0)");
   if (in->n_src > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "n_src exceeds the handle's max_batch");
   if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (clear) {
-    if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
-    if (in->min_d2 > h->dist_cap2 || in->n_penalty > h->dist_cap2)  // direct_cluster_grid_path_clear_batch's cap rule
-      return cfail(DIRECT_ERR_INVALID, "min_d2 or n_penalty above the cap2 the distance field was built with");
-  }
+  if (clear)
+    if (const char* why = clear_field_refusal(h, in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
     return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ae));
-  if (in->n_penalty > 0 && !h->path_pen) {
-    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->path_pen, (size_t)gp::kMaxPenalty * sizeof(double))});
-    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: table allocation: ") + hipGetErrorString(ae));
-  }
+  if (const direct_status_t us = upload_penalty(h, in->n_penalty, in->penalty, "grid_path_fan_batch"); us != DIRECT_OK) return us;
   PathDev& P = h->P;
-  PathClearDev C = {};
-  if (clear) {
-    C.d2 = h->dist[0];
-    C.pen = in->n_penalty > 0 ? h->path_pen : nullptr;
-    C.n_pen = in->n_penalty; C.min_d2 = in->min_d2;
-  }
+  const PathClearDev C = clear ? clear_dev(h, in->min_d2, in->n_penalty) : PathClearDev{};
   const size_t ns = (size_t)in->n_src, ng = (size_t)in->n_goal, cap = (size_t)in->path_capacity;
   // the goals, their sources and the grouping by source (a counting sort: the goals of a source in the caller's order), one array
-  std::vector<int> meta(3 * ng + ng + ng + ns + 1), ends(ns * 6);
+  std::vector<int> meta(3 * ng + ng + ng + ns + 1);
   int *m_goal = meta.data(), *m_src = m_goal + 3 * ng, *m_order = m_src + ng, *m_off = m_order + ng;
   std::copy(in->goals, in->goals + 3 * ng, m_goal);
   for (size_t j = 0; j < ng; j++) m_src[j] = in->goal_src ? in->goal_src[j] : 0;
@@ -1877,8 +1862,7 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
     std::vector<int> at(m_off, m_off + ns);
     for (size_t j = 0; j < ng; j++) m_order[at[m_src[j]]++] = (int)j;
   }
-  for (size_t s = 0; s < ns; s++)
-    for (int a = 0; a < 3; a++) ends[6 * s + a] = ends[6 * s + 3 + a] = in->sources[3 * s + a];  // k_path_init's (start, goal) = (source, source)
+  const std::vector<int> ends = pack_ends(ns, in->sources, in->sources);  // k_path_init's (start, goal) = (source, source)
   // Two blocks, both or neither: the workspace (host inputs and scratch, whatever `mem` is) and the staging of host outputs.
   FanDev F = {};
   F.n_src = in->n_src; F.n_goal = in->n_goal;
@@ -1904,14 +1888,24 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   F.goals = d_meta; F.gsrc = d_meta + 3 * ng; F.order = F.gsrc + ng; F.off = F.order + ng;
   P.cap = (int)cap;
   CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), ns * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (in->n_penalty > 0)
-    CHIP_TRY(hipMemcpyAsync(h->path_pen, in->penalty, (size_t)in->n_penalty * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hs::start(h->ev, h->stream));
   hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), in->n_src), dim3(256), 0, h->stream, P);
   CHIP_TRY(hipGetLastError());
   const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
   int done = 0;
-  hipError_t e = clear ? fan_rounds<true>(h, C, F, lim, &done) : fan_rounds<false>(h, C, F, lim, &done);
+  // k_fan_bound goes in front of every round, or of every batch of rounds (fan_bound_every: 1 or gp::kFanRoundsPerCheck, and a
+  // batch starts at a multiple of that)
+  const dim3 tiles(P.ntiles, in->n_src);
+  hipError_t e = path_rounds(h, ns, lim, &done, [&](int r) {
+    const bool bound = r % h->fan_bound_every == 0;
+    if (clear) {
+      if (bound) hipLaunchKernelGGL(k_fan_bound<true>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
+      hipLaunchKernelGGL(k_fan_relax<true>, tiles, dim3(256), 0, h->stream, P, C, (const double*)F.bound, r);
+    } else {
+      if (bound) hipLaunchKernelGGL(k_fan_bound<false>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
+      hipLaunchKernelGGL(k_fan_relax<false>, tiles, dim3(256), 0, h->stream, P, C, (const double*)F.bound, r);
+    }
+  });
   if (e == hipSuccess) {
     if (clear)
       hipLaunchKernelGGL(k_fan_trace<true>, dim3(in->n_goal), dim3(64), 0, h->stream, P, C, F, done, (int32_t*)dev[0], (int32_t*)dev[1],
@@ -1923,11 +1917,7 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::stage_download(so, h->stream, e);
-  if (e == hipSuccess && out->dist)
-    e = hipMemcpyAsync(out->dist, P.field, ns * (size_t)P.G * sizeof(double),
-                       in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
-  e = hs::drain(h->stream, e);
+  e = hs::drain(h->stream, download_fields(h, out->dist, ns, in->mem, hs::stage_download(so, h->stream, e)));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
