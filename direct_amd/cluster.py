@@ -328,21 +328,36 @@ class ClusterGenerator:
         float64 or None: NumPy arrays, or device tensors (then every output is a device tensor too).
         -> dict(status, verdict, t_free, first [B][2], hit_box [B][6], seg_first [B][N]); count=True adds the diagnostics unresolved
         (segment slots the first pass left to the deep pass) and box_tests, at the price of one atomic add per wave."""
+        par = PlanCheckIn(depth=int(depth), outside_blocks=int(bool(outside_blocks)), resolution=float(resolution), margin=float(margin))
+        i32, f64 = np.int32, np.float64
+        _keep, out, ptr = self._plan_rows(par, n_seg, T, map_lower, bez, poly, t_from, (
+            ("status", (), i32, 0), ("verdict", (), i32, 0), ("t_free", (), f64, 0), ("first", (2,), i32, 0), ("hit_box", (6,), i32, 0),
+            ("seg_first", ("N",), i32, -1)))
+        stats = np.zeros(2, np.int64)
+        o = PlanCheckOut(*[ptr(a) for a in out.values()], stats.ctypes.data if count else None)  # the table's order is the struct's
+        _check(_lib().direct_cluster_plan_check_batch(self.h, C.addressof(par), C.addressof(o)))
+        if count:
+            out.update(unresolved=int(stats[0]), box_tests=int(stats[1]))
+        return out
+
+    @staticmethod
+    def _plan_rows(par, n_seg, T, map_lower, bez, poly, t_from, outputs):
+        """The front of check_plans and plan_clearance, for NumPy arrays and device tensors alike: the inputs in the C-ABI's layout
+        (float32 T keeps float32, anything else becomes float64, coefficients follow T), the zeroed outputs of the table `outputs`,
+        rows of (name, shape behind [B] with "N" for n_seg_max, NumPy dtype, fill of a device tensor) in the output struct's order,
+        and - written INTO `par` - the fields the two input structs share: mem, dtype, map_lower, batch, n_seg_max, n_seg, T, bez,
+        poly, t_from.
+        -> (the inputs, to be kept alive over the call; dict of outputs; array -> address)"""
         assert (bez is None) != (poly is None), "exactly one of bez and poly"
         coef = bez if poly is None else poly
-        lower = np.asarray(map_lower, np.float64).reshape(3)
-        par = PlanCheckIn(depth=int(depth), outside_blocks=int(bool(outside_blocks)), resolution=float(resolution), margin=float(margin),
-                          map_lower=(C.c_double * 3)(*lower))
-        stats = np.zeros(2, np.int64)
-        if isinstance(T, np.ndarray) or not hasattr(T, "data_ptr"):
+        host = isinstance(T, np.ndarray) or not hasattr(T, "data_ptr")
+        if host:
             T = np.asarray(T)
             real = np.float32 if T.dtype == np.float32 else np.float64
             T, coef = np.ascontiguousarray(T, real), np.ascontiguousarray(coef, real)
             n_seg = np.ascontiguousarray(n_seg, np.int32)
-            B, N = T.shape
             tf = None if t_from is None else np.ascontiguousarray(t_from, np.float64)
-            out = dict(status=np.zeros(B, np.int32), verdict=np.zeros(B, np.int32), t_free=np.zeros(B, np.float64),
-                       first=np.zeros((B, 2), np.int32), hit_box=np.zeros((B, 6), np.int32), seg_first=np.zeros((B, N), np.int32))
+            mk = lambda shape, dt, fill: np.zeros(shape, dt)
             ptr = lambda a: a.ctypes.data
             par.mem, par.dtype = abi.MEM_HOST, abi.F32 if real == np.float32 else abi.F64
         else:
@@ -351,25 +366,21 @@ class ClusterGenerator:
             T, coef = T.to(real).contiguous(), coef.to(real).contiguous()
             n_seg = n_seg.to(torch.int32).contiguous()
             assert T.is_cuda and coef.is_cuda and n_seg.is_cuda
-            B, N = T.shape
             tf = None if t_from is None else t_from.to(torch.float64).contiguous()
-            mk = lambda shape, dt, fill=0: torch.full(shape, fill, dtype=dt, device=T.device)
-            out = dict(status=mk((B,), torch.int32), verdict=mk((B,), torch.int32), t_free=mk((B,), torch.float64),
-                       first=mk((B, 2), torch.int32), hit_box=mk((B, 6), torch.int32), seg_first=mk((B, N), torch.int32, -1))
-            torch.cuda.current_stream(T.device).synchronize()  # the handle's stream is not torch's
+            mk = lambda shape, dt, fill: torch.full(shape, fill, dtype=getattr(torch, np.dtype(dt).name), device=T.device)
             ptr = lambda a: a.data_ptr()
             par.mem, par.dtype = abi.MEM_DEVICE, abi.F32 if real == torch.float32 else abi.F64
+        B, N = T.shape
+        out = {k: mk((B,) + tuple(N if s == "N" else s for s in shape), dt, fill) for k, shape, dt, fill in outputs}
+        if not host:
+            torch.cuda.current_stream(T.device).synchronize()  # the handle's stream is not torch's
         assert tuple(coef.shape) == (B, N, 18) and tuple(n_seg.shape) == (B,) and (tf is None or tuple(tf.shape) == (B,))
+        par.map_lower = (C.c_double * 3)(*np.asarray(map_lower, np.float64).reshape(3))
         par.batch, par.n_seg_max = B, N
         par.n_seg, par.T = ptr(n_seg), ptr(T)
         par.bez, par.poly = (ptr(coef), None) if poly is None else (None, ptr(coef))
         par.t_from = None if tf is None else ptr(tf)
-        o = PlanCheckOut(*[ptr(out[k]) for k in ("status", "verdict", "t_free", "first", "hit_box", "seg_first")],
-                         stats.ctypes.data if count else None)
-        _check(_lib().direct_cluster_plan_check_batch(self.h, C.addressof(par), C.addressof(o)))
-        if count:
-            out.update(unresolved=int(stats[0]), box_tests=int(stats[1]))
-        return out
+        return (n_seg, T, coef, tf), out, ptr
 
     def build_distance_field(self, cap_vox=0):
         """The exact squared Euclidean distance field of the map the handle holds now (direct_cluster_distance_field), in voxel
@@ -397,43 +408,12 @@ class ClusterGenerator:
         (direct_cluster_plan_clearance_batch; build_distance_field must have run since the map last changed).  Inputs as check_plans;
         radius >= 0: from when on the plan is closer than that.  NumPy arrays, or device tensors (then every output is one too).
         -> dict(status, clearance, where [B][2], t_min, verdict, t_free, seg_clearance [B][N])"""
-        assert (bez is None) != (poly is None), "exactly one of bez and poly"
-        coef = bez if poly is None else poly
-        lower = np.asarray(map_lower, np.float64).reshape(3)
-        par = PlanClearIn(depth=int(depth), resolution=float(resolution), radius=float(radius), map_lower=(C.c_double * 3)(*lower))
-        if isinstance(T, np.ndarray) or not hasattr(T, "data_ptr"):
-            T = np.asarray(T)
-            real = np.float32 if T.dtype == np.float32 else np.float64
-            T, coef = np.ascontiguousarray(T, real), np.ascontiguousarray(coef, real)
-            n_seg = np.ascontiguousarray(n_seg, np.int32)
-            B, N = T.shape
-            tf = None if t_from is None else np.ascontiguousarray(t_from, np.float64)
-            out = dict(status=np.zeros(B, np.int32), clearance=np.zeros(B, np.float64), where=np.zeros((B, 2), np.int32),
-                       t_min=np.zeros(B, np.float64), verdict=np.zeros(B, np.int32), t_free=np.zeros(B, np.float64),
-                       seg_clearance=np.zeros((B, N), np.float64))
-            ptr = lambda a: a.ctypes.data
-            par.mem, par.dtype = abi.MEM_HOST, abi.F32 if real == np.float32 else abi.F64
-        else:
-            import torch
-            real = torch.float32 if T.dtype == torch.float32 else torch.float64
-            T, coef = T.to(real).contiguous(), coef.to(real).contiguous()
-            n_seg = n_seg.to(torch.int32).contiguous()
-            assert T.is_cuda and coef.is_cuda and n_seg.is_cuda
-            B, N = T.shape
-            tf = None if t_from is None else t_from.to(torch.float64).contiguous()
-            mk = lambda shape, dt, fill=0: torch.full(shape, fill, dtype=dt, device=T.device)
-            out = dict(status=mk((B,), torch.int32), clearance=mk((B,), torch.float64), where=mk((B, 2), torch.int32),
-                       t_min=mk((B,), torch.float64), verdict=mk((B,), torch.int32), t_free=mk((B,), torch.float64),
-                       seg_clearance=mk((B, N), torch.float64, float("nan")))
-            torch.cuda.current_stream(T.device).synchronize()  # the handle's stream is not torch's
-            ptr = lambda a: a.data_ptr()
-            par.mem, par.dtype = abi.MEM_DEVICE, abi.F32 if real == torch.float32 else abi.F64
-        assert tuple(coef.shape) == (B, N, 18) and tuple(n_seg.shape) == (B,) and (tf is None or tuple(tf.shape) == (B,))
-        par.batch, par.n_seg_max = B, N
-        par.n_seg, par.T = ptr(n_seg), ptr(T)
-        par.bez, par.poly = (ptr(coef), None) if poly is None else (None, ptr(coef))
-        par.t_from = None if tf is None else ptr(tf)
-        o = PlanClearOut(*[ptr(out[k]) for k in ("status", "clearance", "where", "t_min", "verdict", "t_free", "seg_clearance")])
+        par = PlanClearIn(depth=int(depth), resolution=float(resolution), radius=float(radius))
+        i32, f64 = np.int32, np.float64
+        _keep, out, ptr = self._plan_rows(par, n_seg, T, map_lower, bez, poly, t_from, (
+            ("status", (), i32, 0), ("clearance", (), f64, 0), ("where", (2,), i32, 0), ("t_min", (), f64, 0), ("verdict", (), i32, 0),
+            ("t_free", (), f64, 0), ("seg_clearance", ("N",), f64, float("nan"))))
+        o = PlanClearOut(*[ptr(a) for a in out.values()])  # the table's order is the struct's
         _check(_lib().direct_cluster_plan_clearance_batch(self.h, C.addressof(par), C.addressof(o)))
         return out
 

@@ -1124,6 +1124,56 @@ direct_status_t upload_penalty(direct_cluster_handle_t h, int32_t n_penalty, con
   return DIRECT_OK;
 }
 
+// plan_check_batch and plan_clearance_batch, whose input structs share their field names.  What both refuse comes in two ordered
+// groups, each call having checks of its own between and behind them; `extent` is the call's one length, margin or radius.
+template <class In, class Out>
+const char* plan_rows_refusal(direct_cluster_handle_t h, const In* in, const Out* out) {
+  if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return "null argument";
+  if (in->batch <= 0 || in->n_seg_max <= 0) return "batch and n_seg_max must be positive";
+  if ((in->bez != nullptr) == (in->poly != nullptr)) return "exactly one of bez and poly";
+  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE";
+  if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return "dtype is neither DIRECT_F32 nor DIRECT_F64";
+  if (in->depth < 0 || in->depth > pk::kMaxDepth) return "depth outside [0, 12]";
+  return nullptr;
+}
+template <class In>
+const char* plan_map_refusal(direct_cluster_handle_t h, const In* in, double extent, const char* extent_refusal) {
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return "resolution must be finite and positive";
+  if (!std::isfinite(extent) || !(extent >= 0.0)) return extent_refusal;
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(in->map_lower[a])) return "map_lower must be finite";
+  return h->have_map ? nullptr : "the handle has no map";
+}
+// Their last refusal, then the row view (without S), the grid fields both Grids have and the four inputs on the call's Stage
+template <class In, class Grid>
+direct_status_t plan_rows_stage(direct_cluster_handle_t h, hs::Stage& st, const In* in, PlanRows& R, Grid& G) {
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->n_seg_max, r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  for (int a = 0; a < 3; a++) G.lower[a] = in->map_lower[a];
+  G.inv = 1.0 / in->resolution;
+  G.size[0] = h->D.max_x; G.size[1] = h->D.max_y; G.size[2] = h->D.max_z;
+  R.batch = in->batch; R.nmax = in->n_seg_max; R.depth = in->depth; R.poly = in->poly != nullptr; R.has_from = in->t_from != nullptr;
+  hs::stage_in(st, &R.n_seg, in->n_seg, B * 4);
+  hs::stage_in(st, &R.T, in->T, slots * r);
+  hs::stage_in(st, &R.coef, in->poly ? in->poly : in->bez, slots * 18 * r);
+  hs::stage_in(st, &R.t_from, in->t_from, B * 8);
+  return DIRECT_OK;
+}
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }  // bytes rounded up to the 256-byte pieces both workspaces are laid out in
+// Their timed part and way back, after stage_upload: launch() enqueues the kernels between the handle's two events, the staged
+// outputs come back, after() enqueues what else the call reads, the stream drains.  `who` opens the message of a device error.
+template <class Launch, class After>
+direct_status_t plan_run(direct_cluster_handle_t h, const hs::Stage& st, const char* who, Launch launch, After after) {
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = launch();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(st, h->stream, e);
+  if (e == hipSuccess) e = after();
+  e = hs::drain(h->stream, e);
+  return e == hipSuccess ? DIRECT_OK : cfail(DIRECT_ERR_DEVICE, std::string(who) + hipGetErrorString(e));
+}
+
 PathClearDev clear_dev(direct_cluster_handle_t h, int32_t min_d2, int32_t n_penalty) {
   PathClearDev C = {};
   C.d2 = h->dist[0];
@@ -1561,46 +1611,25 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
 }
 
 direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in, direct_plan_check_out_t* out) {
-  if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (in->batch <= 0 || in->n_seg_max <= 0) return cfail(DIRECT_ERR_INVALID, "batch and n_seg_max must be positive");
-  if ((in->bez != nullptr) == (in->poly != nullptr)) return cfail(DIRECT_ERR_INVALID, "exactly one of bez and poly");
-  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "dtype is neither DIRECT_F32 nor DIRECT_F64");
-  if (in->depth < 0 || in->depth > pk::kMaxDepth) return cfail(DIRECT_ERR_INVALID, "depth outside [0, 12]");
-  if (in->outside_blocks != 0 && in->outside_blocks != 1) return cfail(DIRECT_ERR_INVALID, "outside_blocks is neither 0 nor 1");
-  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
-  if (!std::isfinite(in->margin) || !(in->margin >= 0.0)) return cfail(DIRECT_ERR_INVALID, "margin must be finite and not negative");
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  const size_t B = (size_t)in->batch, nm = (size_t)in->n_seg_max, slots = B * nm;
-  if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  const Dev& D = h->D;
-  const size_t r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  // workspace: counters, S, per-slot leaves, unresolved list
-  const size_t w_S = up(256), w_first = w_S + up(B * (nm + 1) * sizeof(double)), w_list = w_first + up(slots * sizeof(int)),
-               w_total = w_list + up(slots * sizeof(int));
-  CHIP_TRY(hs::grow(h->plan_ws, h->stream, w_total));
-  PlanDev A = {};
-  for (int a = 0; a < 3; a++) A.G.lower[a] = in->map_lower[a];
-  A.G.inv = 1.0 / in->resolution;
-  A.G.margin = in->margin;
-  A.G.size[0] = D.max_x; A.G.size[1] = D.max_y; A.G.size[2] = D.max_z;
-  A.G.outside_blocks = in->outside_blocks;
-  A.batch = in->batch; A.nmax = in->n_seg_max; A.depth = in->depth; A.poly = in->poly != nullptr; A.has_from = in->t_from != nullptr;
-  A.count = out->stats != nullptr;
-  char* W = (char*)h->plan_ws.p;
-  A.n_list = (unsigned*)W; A.n_tests = (unsigned long long*)(W + 8);
-  A.S = (double*)(W + w_S); A.ws_first = (int*)(W + w_first); A.list = (int*)(W + w_list);
+  const char* why = plan_rows_refusal(h, in, out);
+  if (!why && in->outside_blocks != 0 && in->outside_blocks != 1) why = "outside_blocks is neither 0 nor 1";
+  if (!why) why = plan_map_refusal(h, in, in->margin, "margin must be finite and not negative");
+  if (why) return cfail(DIRECT_ERR_INVALID, why);
   // host arrays go through one staging block: n_seg, T, coef, t_from in; the six outputs back, of which seg_first alone is
   // filled (0xff: entries past n_seg read -1)
   hs::Stage st(in->mem == DIRECT_MEM_HOST);
-  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
-  hs::stage_in(st, &A.T, in->T, slots * r);
-  hs::stage_in(st, &A.coef, in->poly ? in->poly : in->bez, slots * 18 * r);
-  hs::stage_in(st, &A.t_from, in->t_from, B * 8);
+  PlanDev A = {};
+  if (const direct_status_t rc = plan_rows_stage(h, st, in, A.R, A.G)) return rc;
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->n_seg_max;
+  // workspace: counters, S, per-slot leaves, unresolved list
+  const size_t w_S = up256(256), w_first = w_S + up256((B + slots) * sizeof(double)), w_list = w_first + up256(slots * sizeof(int));
+  CHIP_TRY(hs::grow(h->plan_ws, h->stream, w_list + up256(slots * sizeof(int))));
+  A.G.margin = in->margin;
+  A.G.outside_blocks = in->outside_blocks;
+  A.count = out->stats != nullptr;
+  char* W = (char*)h->plan_ws.p;
+  A.n_list = (unsigned*)W; A.n_tests = (unsigned long long*)(W + 8);
+  A.R.S = (double*)(W + w_S); A.ws_first = (int*)(W + w_first); A.list = (int*)(W + w_list);
   hs::stage_out(st, &A.status, out->status, B * 4);
   hs::stage_out(st, &A.verdict, out->verdict, B * 4);
   hs::stage_out(st, &A.t_free, out->t_free, B * 8);
@@ -1608,17 +1637,14 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
   hs::stage_out(st, &A.hit_box, out->hit_box, B * 24);
   hs::stage_out(st, &A.seg_first, out->seg_first, slots * 4, 0xff);
   CHIP_TRY(hs::stage_upload(st, h->plan_io, h->stream));
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  hipError_t e = hipMemsetAsync(h->plan_ws.p, 0, 16, h->stream);
-  if (e == hipSuccess) e = in->dtype == DIRECT_F32 ? plan_check_launch<float>(D, A, h->stream) : plan_check_launch<double>(D, A, h->stream);
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::stage_download(st, h->stream, e);
   unsigned long long cnt[2] = {0, 0};
-  if (e == hipSuccess && out->stats) e = hipMemcpyAsync(cnt, h->plan_ws.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
-  e = hs::drain(h->stream, e);
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_check_batch: ") + hipGetErrorString(e));
-  if (out->stats) { out->stats[0] = (int64_t)(cnt[0] & 0xffffffffull); out->stats[1] = (int64_t)cnt[1]; }
-  return DIRECT_OK;
+  const direct_status_t rc = plan_run(h, st, "plan_check_batch: ", [&] {
+    const hipError_t e = hipMemsetAsync(W, 0, 16, h->stream);
+    if (e != hipSuccess) return e;
+    return in->dtype == DIRECT_F32 ? plan_check_launch<float>(h->D, A, h->stream) : plan_check_launch<double>(h->D, A, h->stream);
+  }, [&] { return out->stats ? hipMemcpyAsync(cnt, W, sizeof(cnt), hipMemcpyDeviceToHost, h->stream) : hipSuccess; });
+  if (rc == DIRECT_OK && out->stats) { out->stats[0] = (int64_t)(cnt[0] & 0xffffffffull); out->stats[1] = (int64_t)cnt[1]; }
+  return rc;
 }
 
 direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t cap_vox, int64_t* stats) {
@@ -1665,44 +1691,23 @@ direct_status_t direct_cluster_get_distance_field(direct_cluster_handle_t h, int
 }
 
 direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, const direct_plan_clear_in_t* in, direct_plan_clear_out_t* out) {
-  if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (in->batch <= 0 || in->n_seg_max <= 0) return cfail(DIRECT_ERR_INVALID, "batch and n_seg_max must be positive");
-  if ((in->bez != nullptr) == (in->poly != nullptr)) return cfail(DIRECT_ERR_INVALID, "exactly one of bez and poly");
-  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "dtype is neither DIRECT_F32 nor DIRECT_F64");
-  if (in->depth < 0 || in->depth > pk::kMaxDepth) return cfail(DIRECT_ERR_INVALID, "depth outside [0, 12]");
-  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
-  if (!std::isfinite(in->radius) || !(in->radius >= 0.0)) return cfail(DIRECT_ERR_INVALID, "radius must be finite and not negative");
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
-  const size_t B = (size_t)in->batch, nm = (size_t)in->n_seg_max, slots = B * nm;
-  if (slots >= (1ull << 31)) return cfail(DIRECT_ERR_UNSUPPORTED, "batch * n_seg_max of 2^31 or more");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  const Dev& D = h->D;
-  const size_t r = in->dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  // workspace: S, then per slot the minimum, its leaf, the first leaf below the radius
-  const size_t w_min = up(B * (nm + 1) * sizeof(double)), w_leaf = w_min + up(slots * sizeof(double)), w_below = w_leaf + up(slots * sizeof(int)),
-               w_total = w_below + up(slots * sizeof(int));
-  CHIP_TRY(hs::grow(h->clear_ws, h->stream, w_total));
-  char* W = (char*)h->clear_ws.p;
-  ClearDev A = {};
-  for (int a = 0; a < 3; a++) A.G.lower[a] = in->map_lower[a];
-  A.G.inv = 1.0 / in->resolution;
-  A.G.resolution = in->resolution;
-  A.G.size[0] = D.max_x; A.G.size[1] = D.max_y; A.G.size[2] = D.max_z;
-  A.batch = in->batch; A.nmax = in->n_seg_max; A.depth = in->depth; A.poly = in->poly != nullptr; A.has_from = in->t_from != nullptr;
-  A.radius = in->radius;
-  A.field = h->dist[0]; A.YZ = D.max_yz; A.Z = D.max_z;
-  A.S = (double*)W; A.ws_min = (double*)(W + w_min); A.ws_leaf = (int*)(W + w_leaf); A.ws_below = (int*)(W + w_below);
+  const char* why = plan_rows_refusal(h, in, out);
+  if (!why) why = plan_map_refusal(h, in, in->radius, "radius must be finite and not negative");
+  if (!why && !h->dist_valid) why = "no valid distance field: call direct_cluster_distance_field after the map changes";
+  if (why) return cfail(DIRECT_ERR_INVALID, why);
   // host arrays go through one staging block of the call's own; seg_clearance alone is filled (0xff: entries past n_seg read NaN)
   hs::Stage st(in->mem == DIRECT_MEM_HOST);
-  hs::stage_in(st, &A.n_seg, in->n_seg, B * 4);
-  hs::stage_in(st, &A.T, in->T, slots * r);
-  hs::stage_in(st, &A.coef, in->poly ? in->poly : in->bez, slots * 18 * r);
-  hs::stage_in(st, &A.t_from, in->t_from, B * 8);
+  ClearDev A = {};
+  if (const direct_status_t rc = plan_rows_stage(h, st, in, A.R, A.G)) return rc;
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->n_seg_max;
+  // workspace: S, then per slot the minimum, its leaf, the first leaf below the radius
+  const size_t w_min = up256((B + slots) * sizeof(double)), w_leaf = w_min + up256(slots * sizeof(double)), w_below = w_leaf + up256(slots * sizeof(int));
+  CHIP_TRY(hs::grow(h->clear_ws, h->stream, w_below + up256(slots * sizeof(int))));
+  char* W = (char*)h->clear_ws.p;
+  A.G.resolution = in->resolution;
+  A.radius = in->radius;
+  A.field = h->dist[0]; A.YZ = h->D.max_yz; A.Z = h->D.max_z;
+  A.R.S = (double*)W; A.ws_min = (double*)(W + w_min); A.ws_leaf = (int*)(W + w_leaf); A.ws_below = (int*)(W + w_below);
   hs::stage_out(st, &A.status, out->status, B * 4);
   hs::stage_out(st, &A.clearance, out->clearance, B * 8);
   hs::stage_out(st, &A.where, out->where, B * 8);
@@ -1711,15 +1716,9 @@ direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, c
   hs::stage_out(st, &A.t_free, out->t_free, B * 8);
   hs::stage_out(st, &A.seg_clearance, out->seg_clearance, slots * 8, 0xff);
   CHIP_TRY(hs::stage_upload(st, h->clear_io, h->stream));
-  PlanDev P = {};  // what k_plan_starts reads
-  P.batch = A.batch; P.nmax = A.nmax; P.has_from = A.has_from; P.n_seg = A.n_seg; P.T = A.T; P.t_from = A.t_from; P.S = (double*)W;
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  hipError_t e = in->dtype == DIRECT_F32 ? plan_clear_launch<float>(P, A, h->stream) : plan_clear_launch<double>(P, A, h->stream);
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::stage_download(st, h->stream, e);
-  e = hs::drain(h->stream, e);
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("plan_clearance_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  return plan_run(h, st, "plan_clearance_batch: ",
+                  [&] { return in->dtype == DIRECT_F32 ? plan_clear_launch<float>(A, h->stream) : plan_clear_launch<double>(A, h->stream); },
+                  [] { return hipSuccess; });
 }
 
 direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out) {

@@ -2,6 +2,7 @@
 // direct_cluster.hip inside its anonymous namespace.  The arithmetic is plan_check_math.h's, shared with the CPU tests; the box test
 // is box_obstacles() on the handle's summed-area table (eight loads), asked for the box's intersection with the map only.
 //
+//   PlanRows       what every kernel over plan rows reads, with the spellings that go with it: plan_clear.h's kernels use both.
 //   k_plan_starts  one thread per row: the segment start times S (the evaluation's left-to-right sum) into the workspace and the
 //                  row's validity as far as n_seg, T and t_from decide it (S[0] = NaN marks an invalid row, as k_eval_starts does).
 //   k_plan_seg     one lane per (row, segment) slot: control points in metres, then the descent from the segment's root with a
@@ -27,13 +28,31 @@ namespace pk = direct::plancheck;
 constexpr int kSegBudget = 8;       // box tests a slot may spend in k_plan_seg
 constexpr int kDeepBlocks = 1024;   // workgroups of k_plan_deep (4 waves each)
 
-struct PlanDev {
-  pk::Grid G;
-  int batch, nmax, depth, poly, has_from, count;
+// The caller's rows and the start times k_plan_starts leaves in the call's workspace; slot g is segment g % nmax of row g / nmax.
+struct PlanRows {
+  int batch, nmax, depth, poly, has_from;
   const int32_t* n_seg;
   const void *T, *coef;             // the storage type's
   const double* t_from;
   double* S;                        // [batch][nmax + 1]
+};
+
+template <typename St>  // control points in metres of slot g, whose duration is Ti; 0 when they are not usable
+__device__ __forceinline__ int plan_ctrl(const PlanRows& R, int g, double Ti, double* P) {
+  const St* c = (const St*)R.coef + (size_t)g * 18;
+  return R.poly ? pk::ctrl_from_poly(c, Ti, P) : pk::ctrl_from_bez(c, Ti, P);
+}
+struct PlanSlot { int b, i; };  // row and segment
+__device__ __forceinline__ PlanSlot plan_slot(const PlanRows& R, int g) { return {g / R.nmax, g - g / R.nmax * R.nmax}; }
+__device__ __forceinline__ double* plan_S(const PlanRows& R, int b) { return R.S + (size_t)b * (R.nmax + 1); }
+__device__ __forceinline__ bool plan_row_valid(const double* S) { return S[0] == 0.0; }  // k_plan_starts left no NaN there
+__device__ __forceinline__ double plan_t_from(const PlanRows& R, int b) { return R.has_from ? R.t_from[b] : 0.0; }
+__device__ __forceinline__ int plan_lane_depth(const PlanRows& R) { return R.depth < 6 ? R.depth : 6; }
+
+struct PlanDev {
+  pk::Grid G;                       // first: the row fields then sit where the kernels' arguments always had them
+  PlanRows R;
+  int count;
   int* ws_first;                    // [batch][nmax] a segment's first blocked judged leaf, kNone or kBadCoef
   int* list;                        // [batch * nmax] unresolved slots
   unsigned* n_list;                 // [1]
@@ -42,12 +61,6 @@ struct PlanDev {
   double* t_free;
 };
 
-template <typename St>
-__device__ __forceinline__ int plan_ctrl(const PlanDev& A, int g, double Ti, double* P) {
-  const St* c = (const St*)A.coef + (size_t)g * 18;
-  return A.poly ? pk::ctrl_from_poly(c, Ti, P) : pk::ctrl_from_bez(c, Ti, P);
-}
-
 __device__ __forceinline__ void plan_count(const PlanDev& A, long long tests) {
   if (!A.count) return;
   for (int o = 32; o > 0; o >>= 1) tests += __shfl_down(tests, o);
@@ -55,31 +68,32 @@ __device__ __forceinline__ void plan_count(const PlanDev& A, long long tests) {
 }
 
 template <typename St>
-__global__ __launch_bounds__(64) void k_plan_starts(PlanDev A) {
+__global__ __launch_bounds__(64) void k_plan_starts(PlanRows R) {
   const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= A.batch) return;
-  double* S = A.S + (size_t)b * (A.nmax + 1);
-  int ok = direct::eval::row_starts((const St*)A.T + (size_t)b * A.nmax, A.n_seg[b], A.nmax, S);
-  if (A.has_from && A.t_from[b] != A.t_from[b]) ok = 0;
+  if (b >= R.batch) return;
+  double* S = plan_S(R, b);
+  int ok = direct::eval::row_starts((const St*)R.T + (size_t)b * R.nmax, R.n_seg[b], R.nmax, S);
+  if (R.has_from && R.t_from[b] != R.t_from[b]) ok = 0;
   if (!ok) S[0] = __builtin_nan("");
 }
 
 template <typename St>
 __global__ __launch_bounds__(256) void k_plan_seg(Dev D, PlanDev A) {
-  const int g = blockIdx.x * 256 + threadIdx.x, total = A.batch * A.nmax;
+  const PlanRows& R = A.R;
+  const int g = blockIdx.x * 256 + threadIdx.x, total = R.batch * R.nmax;
   const auto occupied = [&](const int* lo, const int* hi) { return box_obstacles(D, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]) > 0; };
   const auto visit = [](int, int, const int*, const int*, int) {};
   long long tests = 0;
   int open = 0;
   if (g < total) {
-    const int b = g / A.nmax, i = g - b * A.nmax;
-    const double* S = A.S + (size_t)b * (A.nmax + 1);
-    if (S[0] == 0.0 && i < A.n_seg[b]) {
-      const double Ti = (double)((const St*)A.T)[g];
+    const auto [b, i] = plan_slot(R, g);
+    const double* S = plan_S(R, b);
+    if (plan_row_valid(S) && i < R.n_seg[b]) {
+      const double Ti = (double)((const St*)R.T)[g];
       double P[18];
       int r = pk::kBadCoef;
-      if (plan_ctrl<St>(A, g, Ti, P))
-        r = pk::descend(P, S[i], Ti, A.depth, 0, 0, A.has_from, A.has_from ? A.t_from[b] : 0.0, A.G, occupied, visit, kSegBudget, &tests);
+      if (plan_ctrl<St>(R, g, Ti, P))
+        r = pk::descend(P, S[i], Ti, R.depth, 0, 0, R.has_from, plan_t_from(R, b), A.G, occupied, visit, kSegBudget, &tests);
       if (r == pk::kOpen) open = 1;
       else A.ws_first[g] = r;
     }
@@ -97,21 +111,22 @@ __global__ __launch_bounds__(256) void k_plan_seg(Dev D, PlanDev A) {
 
 template <typename St>
 __global__ __launch_bounds__(256) void k_plan_deep(Dev D, PlanDev A) {
+  const PlanRows& R = A.R;
   const auto occupied = [&](const int* lo, const int* hi) { return box_obstacles(D, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]) > 0; };
   const auto visit = [](int, int, const int*, const int*, int) {};
   const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
   const unsigned n = *A.n_list;  // final: k_plan_seg has ended
-  const int dl = A.depth < 6 ? A.depth : 6;
+  const int dl = plan_lane_depth(R);
   long long tests = 0;
   for (unsigned idx = wave; idx < n; idx += waves) {
-    const int g = A.list[idx], b = g / A.nmax, i = g - b * A.nmax;
-    const double Ti = (double)((const St*)A.T)[g];
+    const int g = A.list[idx];
+    const auto [b, i] = plan_slot(R, g);
+    const double Ti = (double)((const St*)R.T)[g];
     double P[18];
-    (void)plan_ctrl<St>(A, g, Ti, P);  // usable: the slot was listed
+    (void)plan_ctrl<St>(R, g, Ti, P);  // usable: the slot was listed
     int r = pk::kNone;
     if (lane < (1 << dl))
-      r = pk::descend(P, A.S[(size_t)b * (A.nmax + 1) + i], Ti, A.depth, dl, lane, A.has_from, A.has_from ? A.t_from[b] : 0.0, A.G,
-                      occupied, visit, -1, &tests);
+      r = pk::descend(P, plan_S(R, b)[i], Ti, R.depth, dl, lane, R.has_from, plan_t_from(R, b), A.G, occupied, visit, -1, &tests);
     int key = r >= 0 ? r : 0x7fffffff;
     for (int o = 32; o > 0; o >>= 1) {
       const int other = __shfl_xor(key, o);
@@ -124,12 +139,13 @@ __global__ __launch_bounds__(256) void k_plan_deep(Dev D, PlanDev A) {
 
 template <typename St>
 __global__ __launch_bounds__(64) void k_plan_rows(Dev D, PlanDev A) {
+  const PlanRows& R = A.R;
   const auto occupied = [&](const int* lo, const int* hi) { return box_obstacles(D, lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]) > 0; };
   const int b = blockIdx.x, lane = threadIdx.x;
-  const double* S = A.S + (size_t)b * (A.nmax + 1);
-  const int n = A.n_seg[b];
-  const int* ws = A.ws_first + (size_t)b * A.nmax;
-  int valid = S[0] == 0.0 ? 1 : 0;  // wave-uniform
+  const double* S = plan_S(R, b);
+  const int n = R.n_seg[b];
+  const int* ws = A.ws_first + (size_t)b * R.nmax;
+  int valid = plan_row_valid(S) ? 1 : 0;  // wave-uniform
   int best = 0x7fffffff, bad = 0;
   if (valid)
     for (int i = lane; i < n; i += 64) {
@@ -143,22 +159,22 @@ __global__ __launch_bounds__(64) void k_plan_rows(Dev D, PlanDev A) {
   }
   if (__ballot(bad)) valid = 0;
   if (A.seg_first) {
-    const int cnt = n < 0 ? 0 : (n > A.nmax ? A.nmax : n);
-    for (int i = lane; i < cnt; i += 64) A.seg_first[(size_t)b * A.nmax + i] = valid ? ws[i] : -1;
+    const int cnt = n < 0 ? 0 : (n > R.nmax ? R.nmax : n);
+    for (int i = lane; i < cnt; i += 64) A.seg_first[(size_t)b * R.nmax + i] = valid ? ws[i] : -1;
   }
   int verdict = valid ? 0 : -1, seg = -1, leaf = -1, box[6] = {-1, -1, -1, -1, -1, -1};
   double t_free = valid ? S[n] : 0.0;
   if (valid && best != 0x7fffffff) {
-    const int g = b * A.nmax + best;
-    const double Ti = (double)((const St*)A.T)[g];
+    const int g = b * R.nmax + best;
+    const double Ti = (double)((const St*)R.T)[g];
     double P[18], L[18];
-    (void)plan_ctrl<St>(A, g, Ti, P);
+    (void)plan_ctrl<St>(R, g, Ti, P);
     seg = best;
     leaf = ws[best];
-    pk::derive(P, A.depth, leaf, L);
+    pk::derive(P, R.depth, leaf, L);
     int blocked;
     verdict = pk::judge(L, A.G, occupied, box, box + 3, &blocked);
-    t_free = pk::node_time(S[best], Ti, A.depth, leaf);
+    t_free = pk::node_time(S[best], Ti, R.depth, leaf);
   }
   if (lane == 0) {
     A.status[b] = valid ? 0 : -1;
@@ -173,11 +189,11 @@ __global__ __launch_bounds__(64) void k_plan_rows(Dev D, PlanDev A) {
 // Enqueues the four kernels for one storage type; the counters of the workspace have been cleared on the same stream.
 template <typename St>
 hipError_t plan_check_launch(const Dev& D, const PlanDev& A, hipStream_t stream) {
-  const int slots = A.batch * A.nmax;
-  hipLaunchKernelGGL(k_plan_starts<St>, dim3((A.batch + 63) / 64), dim3(64), 0, stream, A);
+  const int slots = A.R.batch * A.R.nmax;
+  hipLaunchKernelGGL(k_plan_starts<St>, dim3((A.R.batch + 63) / 64), dim3(64), 0, stream, A.R);
   hipLaunchKernelGGL(k_plan_seg<St>, dim3((slots + 255) / 256), dim3(256), 0, stream, D, A);
-  if (A.depth > 0)  // at depth 0 the root is the leaf: nothing can stay open
+  if (A.R.depth > 0)  // at depth 0 the root is the leaf: nothing can stay open
     hipLaunchKernelGGL(k_plan_deep<St>, dim3(std::min(kDeepBlocks, (slots + 3) / 4)), dim3(256), 0, stream, D, A);
-  hipLaunchKernelGGL(k_plan_rows<St>, dim3(A.batch), dim3(64), 0, stream, D, A);
+  hipLaunchKernelGGL(k_plan_rows<St>, dim3(A.R.batch), dim3(64), 0, stream, D, A);
   return hipGetLastError();
 }

@@ -1,6 +1,6 @@
 // Kernels of direct_cluster_plan_clearance_batch (include/direct_cluster.h, "metric clearance of plans"); included by
-// direct_cluster.hip inside its anonymous namespace, after plan_check.h.  The arithmetic is plan_clear_math.h's and
-// plan_check_math.h's, shared with the CPU tests; the field is the handle's resident one, read with one load per leaf.
+// direct_cluster.hip inside its anonymous namespace, after plan_check.h, whose PlanRows (with its helpers) and k_plan_starts serve here
+// too.  The arithmetic is plan_clear_math.h's and plan_check_math.h's, shared with the CPU tests; the field is the resident one.
 //
 //   k_plan_starts  plan_check.h's: start times S and the row's validity into the workspace.
 //   k_clear_seg    one wave per (row, segment) slot, a fixed grid striding over the slots.  Lane l owns subtree l of depth
@@ -20,15 +20,11 @@ namespace pcl = direct::planclear;
 constexpr int kClearBlocks = 1024;  // workgroups of k_clear_seg (4 waves each)
 
 struct ClearDev {
+  PlanRows R;
   pcl::Grid G;
-  int batch, nmax, depth, poly, has_from;
   double radius;
   const int32_t* field;             // the resident distance field
   int YZ, Z;
-  const int32_t* n_seg;
-  const void *T, *coef;             // the storage type's
-  const double* t_from;
-  const double* S;                  // [batch][nmax + 1], k_plan_starts'
   double* ws_min;                   // [batch][nmax] a segment's minimum bound
   int* ws_leaf;                     // [batch][nmax] its leaf, kNoLeaf or kBadCoef
   int* ws_below;                    // [batch][nmax] its first leaf below the radius or kNoLeaf
@@ -38,25 +34,24 @@ struct ClearDev {
 
 template <typename St>
 __global__ __launch_bounds__(256) void k_clear_seg(ClearDev A) {
+  const PlanRows& R = A.R;
   const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), waves = gridDim.x * 4;
-  const int total = A.batch * A.nmax;
-  const int dl = A.depth < 6 ? A.depth : 6;
+  const int total = R.batch * R.nmax;
+  const int dl = plan_lane_depth(R);
   const auto d2_at = [&](int i0, int i1, int i2) { return A.field[(size_t)i0 * A.YZ + (size_t)i1 * A.Z + i2]; };
   for (int g = wave; g < total; g += waves) {
-    const int b = g / A.nmax, i = g - b * A.nmax;
-    const double* S = A.S + (size_t)b * (A.nmax + 1);
-    if (!(S[0] == 0.0) || i >= A.n_seg[b]) continue;  // wave-uniform
-    const double Ti = (double)((const St*)A.T)[g];
-    const St* c = (const St*)A.coef + (size_t)g * 18;
+    const auto [b, i] = plan_slot(R, g);
+    const double* S = plan_S(R, b);
+    if (!plan_row_valid(S) || i >= R.n_seg[b]) continue;  // wave-uniform
+    const double Ti = (double)((const St*)R.T)[g];
     double P[18];
-    const int ok = A.poly ? pk::ctrl_from_poly(c, Ti, P) : pk::ctrl_from_bez(c, Ti, P);
-    if (!ok) {  // wave-uniform
-      if (lane == 0) A.ws_leaf[g] = pcl::kBadCoef;
+    if (!plan_ctrl<St>(R, g, Ti, P)) {  // wave-uniform
+      if (lane == 0) A.ws_leaf[g] = pk::kBadCoef;
       continue;
     }
     pcl::SegMin r = {(double)INFINITY, pcl::kNoLeaf, pcl::kNoLeaf};
     if (lane < (1 << dl))
-      r = pcl::subtree_min(P, S[i], Ti, A.depth, dl, lane, A.has_from, A.has_from ? A.t_from[b] : 0.0, A.radius, A.G, d2_at);
+      r = pcl::subtree_min(P, S[i], Ti, R.depth, dl, lane, R.has_from, plan_t_from(R, b), A.radius, A.G, d2_at);
     for (int o = 32; o > 0; o >>= 1) {
       pcl::SegMin other;
       other.best = __shfl_xor(r.best, o);
@@ -74,18 +69,19 @@ __global__ __launch_bounds__(256) void k_clear_seg(ClearDev A) {
 
 template <typename St>
 __global__ __launch_bounds__(64) void k_clear_rows(ClearDev A) {
+  const PlanRows& R = A.R;
   const int b = blockIdx.x, lane = threadIdx.x;
-  const double* S = A.S + (size_t)b * (A.nmax + 1);
-  const int n = A.n_seg[b];
-  const size_t row = (size_t)b * A.nmax;
-  int valid = S[0] == 0.0 ? 1 : 0;  // wave-uniform; a valid row has 1 <= n <= nmax
+  const double* S = plan_S(R, b);
+  const int n = R.n_seg[b];
+  const size_t row = (size_t)b * R.nmax;
+  int valid = plan_row_valid(S) ? 1 : 0;  // wave-uniform; a valid row has 1 <= n <= nmax
   const double inf = (double)INFINITY, nan = __builtin_nan("");
   double best = inf;
   int seg = pcl::kNoLeaf, low = pcl::kNoLeaf, bad = 0;  // segment of the minimum, first segment with a leaf below the radius
   if (valid)
     for (int i = lane; i < n; i += 64) {
       const int leaf = A.ws_leaf[row + i];
-      if (leaf == pcl::kBadCoef) {
+      if (leaf == pk::kBadCoef) {
         bad = 1;
         continue;
       }
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(64) void k_clear_rows(ClearDev A) {
     low = ol < low ? ol : low;
   }
   if (A.seg_clearance) {
-    const int cnt = n < 0 ? 0 : (n > A.nmax ? A.nmax : n);
+    const int cnt = n < 0 ? 0 : (n > R.nmax ? R.nmax : n);
     for (int i = lane; i < cnt; i += 64) A.seg_clearance[row + i] = valid ? A.ws_min[row + i] : nan;
   }
   if (lane != 0) return;
@@ -120,11 +116,11 @@ __global__ __launch_bounds__(64) void k_clear_rows(ClearDev A) {
     if (seg != pcl::kNoLeaf) {
       s_out = seg;
       leaf = A.ws_leaf[row + seg];
-      t_min = pk::node_time(S[seg], (double)((const St*)A.T)[row + seg], A.depth, leaf);
+      t_min = pk::node_time(S[seg], (double)((const St*)R.T)[row + seg], R.depth, leaf);
     }
     if (low != pcl::kNoLeaf) {
       verdict = 1;
-      t_free = pk::node_time(S[low], (double)((const St*)A.T)[row + low], A.depth, A.ws_below[row + low]);
+      t_free = pk::node_time(S[low], (double)((const St*)R.T)[row + low], R.depth, A.ws_below[row + low]);
     }
   }
   A.status[b] = valid ? 0 : -1;
@@ -135,12 +131,12 @@ __global__ __launch_bounds__(64) void k_clear_rows(ClearDev A) {
   if (A.where) { A.where[2 * b] = s_out; A.where[2 * b + 1] = leaf; }
 }
 
-// Enqueues the three kernels for one storage type; P carries what k_plan_starts reads (batch, nmax, n_seg, T, t_from, S).
+// Enqueues the three kernels for one storage type.
 template <typename St>
-hipError_t plan_clear_launch(const PlanDev& P, const ClearDev& A, hipStream_t stream) {
-  const int slots = A.batch * A.nmax;
-  hipLaunchKernelGGL(k_plan_starts<St>, dim3((A.batch + 63) / 64), dim3(64), 0, stream, P);
+hipError_t plan_clear_launch(const ClearDev& A, hipStream_t stream) {
+  const int slots = A.R.batch * A.R.nmax;
+  hipLaunchKernelGGL(k_plan_starts<St>, dim3((A.R.batch + 63) / 64), dim3(64), 0, stream, A.R);
   hipLaunchKernelGGL(k_clear_seg<St>, dim3(std::min(kClearBlocks, (slots + 3) / 4)), dim3(256), 0, stream, A);
-  hipLaunchKernelGGL(k_clear_rows<St>, dim3(A.batch), dim3(64), 0, stream, A);
+  hipLaunchKernelGGL(k_clear_rows<St>, dim3(A.R.batch), dim3(64), 0, stream, A);
   return hipGetLastError();
 }

@@ -30,7 +30,6 @@ namespace pk = direct::plancheck;
 constexpr double kK = 0x1.bb67ae8584cabp-1;  // 0.8660254037844387: sqrt(3)/2 rounded up (the double below is 5e-17 short of it)
 constexpr int kDistNone = 0x7fffffff;        // DIRECT_DIST_NONE
 constexpr int kNoLeaf = 0x7fffffff;          // no such leaf
-constexpr int kBadCoef = -2;                 // the segment's control points are not usable (pk::kBadCoef)
 
 struct Grid {
   double lower[3];

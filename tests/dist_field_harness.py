@@ -123,32 +123,20 @@ def leaf_bounds(L, d2, lower, res):
 
 
 def restate_clearance(inp, d2, depth, radius=0.0, use_t_from=True, lower=LOWER, res=RES):
-    """inp as plan_check_harness.restate takes it; d2: the stored field -> dict of the call's outputs as they read in HOST memory,
+    """inp as plan_check_harness.plan_rows takes it; d2: the stored field -> dict of the call's outputs as they read in HOST memory,
     plus half_max [B] (the largest leaf half-diagonal of the row) and centre_inside [B] (of the minimising leaf's box)"""
-    n_seg = np.asarray(inp["n_seg"], np.int32)
-    T = np.asarray(inp["T"]).astype(np.float64)
-    poly = inp.get("poly") is not None
-    coef = np.asarray(inp["poly"] if poly else inp["bez"]).astype(np.float64)
-    t_from = inp.get("t_from") if use_t_from else None
+    T, t_from, rows = ph.plan_rows(inp, use_t_from)
     B, N = T.shape
     lower = np.asarray(lower, np.float64)
     nan_fill = np.frombuffer(b"\xff" * 8, np.float64)[0]
     out = dict(status=np.zeros(B, np.int32), clearance=np.zeros(B), where=np.full((B, 2), -1, np.int32), t_min=np.zeros(B),
                verdict=np.zeros(B, np.int32), t_free=np.zeros(B), seg_clearance=np.full((B, N), nan_fill),
                half_max=np.zeros(B), centre_inside=np.zeros(B, bool))
-    for b in range(B):
-        n = int(n_seg[b])
-        ok = 1 <= n <= N and bool(np.all(np.isfinite(T[b, :n]) & (T[b, :n] > 0)))
-        ok = ok and not (t_from is not None and np.isnan(t_from[b]))
-        pts = []
-        if ok:
-            pts = [ph.control_points(coef[b, i], T[b, i], poly) for i in range(n)]
-            ok = all(bool(np.all(np.abs(p) <= ph.MAX_COORD)) for p in pts)
+    for b, (n, ok, pts, S) in enumerate(rows):
         if not ok:
             out["status"][b], out["verdict"][b], out["clearance"][b] = -1, INVALID, np.nan
             out["seg_clearance"][b, :max(0, min(n, N))] = np.nan
             continue
-        S = ph.starts(T[b], n)
         out["t_min"][b] = out["t_free"][b] = S[n]
         best, free_found = np.inf, False
         for i in range(n):
@@ -202,12 +190,11 @@ HARNESS = r'''
 #include <vector>
 #include "dist_field_math.h"
 #include "plan_clear_math.h"
+''' + ph.ROW_FRONT + r'''
 namespace dfm = direct::distfield;
 namespace pc = direct::planclear;
-namespace pk = direct::plancheck;
 // field  in: int32 X, Y, Z, cap_vox, reps, pad; uint8 map[G]            out: int32 d2[G]; int64 stats[2]; float64 ms (best of reps)
-// clear  in: int32 B, N, poly, D, has_from, X, Y, Z; float64 lower[3], res, radius; int32 n_seg[B]; float64 T[B][N],
-//            coef[B][N][18], t_from[B] (when has_from); int32 d2[G]
+// clear  in: int32 B, N, poly, D, has_from, X, Y, Z; float64 lower[3], res, radius; the row section; int32 d2[G]
 //        out: int32 status[B], verdict[B], where[B][2]; float64 clearance[B], t_min[B], t_free[B], seg_clearance[B][N]
 static int field(FILE* f, const char* to) {
   int h[6];
@@ -238,45 +225,23 @@ static int clear(FILE* f, const char* to) {
   int h[8];
   double d[5];
   if (fread(h, 4, 8, f) != 8 || fread(d, 8, 5, f) != 5) return 1;
-  const int B = h[0], N = h[1], poly = h[2], D = h[3], has_from = h[4], X = h[5], Y = h[6], Z = h[7];
+  const int B = h[0], N = h[1], D = h[3], has_from = h[4], X = h[5], Y = h[6], Z = h[7];
   const size_t G = (size_t)X * Y * Z;
-  std::vector<int> n_seg(B);
-  std::vector<double> T((size_t)B * N), coef((size_t)B * N * 18), t_from(B, 0.0);
+  Rows R = {B, N, h[2], has_from};
   std::vector<int32_t> d2(G);
-  if (fread(n_seg.data(), 4, B, f) != (size_t)B || fread(T.data(), 8, T.size(), f) != T.size() ||
-      fread(coef.data(), 8, coef.size(), f) != coef.size())
-    return 1;
-  if (has_from && fread(t_from.data(), 8, B, f) != (size_t)B) return 1;
-  if (fread(d2.data(), 4, G, f) != G) return 1;
+  if (!read_rows(f, R) || fread(d2.data(), 4, G, f) != G) return 1;
   pc::Grid grid;
-  for (int a = 0; a < 3; a++) grid.lower[a] = d[a];
+  grid_front(grid, d, d[3], X, Y, Z);
   grid.resolution = d[3];
-  grid.inv = 1.0 / d[3];
-  grid.size[0] = X; grid.size[1] = Y; grid.size[2] = Z;
   const double radius = d[4];
   auto d2_at = [&](int i0, int i1, int i2) { return d2[((size_t)i0 * Y + i1) * Z + i2]; };
   std::vector<int> status(B), verdict(B), where((size_t)B * 2, -1);
-  std::vector<double> clearance(B), t_min(B), t_free(B), seg((size_t)B * N), S(N + 1);
+  std::vector<double> clearance(B), t_min(B), t_free(B), seg((size_t)B * N), S(N + 1), P;
   memset(seg.data(), 0xff, seg.size() * 8);
   const double nan = __builtin_nan("");
   const int dl = D < 6 ? D : 6;
   for (int b = 0; b < B; b++) {
-    const int n = n_seg[b];
-    int ok = 1 <= n && n <= N;
-    if (ok) {
-      S[0] = 0.0;
-      for (int i = 0; i < n; i++) {
-        const double Ti = T[(size_t)b * N + i];
-        ok &= (Ti > 0.0 && Ti <= 1.7976931348623157e308) ? 1 : 0;
-        S[i + 1] = S[i] + Ti;
-      }
-    }
-    if (has_from && t_from[b] != t_from[b]) ok = 0;
-    std::vector<double> P((size_t)(ok ? n : 0) * 18);
-    for (int i = 0; ok && i < n; i++) {
-      const double* c = &coef[((size_t)b * N + i) * 18];
-      ok &= poly ? pk::ctrl_from_poly(c, T[(size_t)b * N + i], &P[i * 18]) : pk::ctrl_from_bez(c, T[(size_t)b * N + i], &P[i * 18]);
-    }
+    const int n = R.n_seg[b], ok = row_front(R, b, S, P);
     status[b] = ok ? 0 : -1;
     verdict[b] = ok ? 0 : -1;
     clearance[b] = ok ? (double)INFINITY : nan;
@@ -286,11 +251,11 @@ static int clear(FILE* f, const char* to) {
       continue;
     }
     for (int i = 0; i < n; i++) {
-      const double Ti = T[(size_t)b * N + i];
+      const double Ti = R.T[(size_t)b * N + i];
       // the kernels' split into subtrees of depth min(D, 6), merged in DESCENDING order: the merge must not care
       pc::SegMin r = {(double)INFINITY, pc::kNoLeaf, pc::kNoLeaf};
       for (int l = (1 << dl) - 1; l >= 0; l--)
-        r = pc::merge(r, pc::subtree_min(&P[i * 18], S[i], Ti, D, dl, l, has_from, t_from[b], radius, grid, d2_at));
+        r = pc::merge(r, pc::subtree_min(&P[i * 18], S[i], Ti, D, dl, l, has_from, R.t_from[b], radius, grid, d2_at));
       seg[(size_t)b * N + i] = r.best;
       if (r.best < clearance[b]) {
         clearance[b] = r.best;
@@ -355,21 +320,11 @@ def run_field(harness, grid, cap_vox=0, reps=1):
 def run_clear(harness, inp, d2, depth, radius=0.0, use_t_from=True, lower=LOWER, res=RES):
     """-> outputs as restate_clearance gives them (without half_max / centre_inside) of plan_clear_math.h on one thread"""
     d, exe = harness
-    poly = inp.get("poly") is not None
-    T = np.ascontiguousarray(np.asarray(inp["T"]).astype(np.float64))
-    coef = np.ascontiguousarray(np.asarray(inp["poly"] if poly else inp["bez"]).astype(np.float64))
-    t_from = inp.get("t_from") if use_t_from else None
-    B, N = T.shape
+    (B, N, poly, has_from), rows = ph.row_section(inp, use_t_from)
     fin, fout = os.path.join(d, "clear_in.bin"), os.path.join(d, "clear_out.bin")
     with open(fin, "wb") as f:
-        np.array([B, N, int(poly), depth, int(t_from is not None)] + list(d2.shape), np.int32).tofile(f)
-        np.array(list(lower) + [res, radius], np.float64).tofile(f)
-        np.ascontiguousarray(inp["n_seg"], np.int32).tofile(f)
-        T.tofile(f)
-        coef.tofile(f)
-        if t_from is not None:
-            np.ascontiguousarray(t_from, np.float64).tofile(f)
-        np.ascontiguousarray(d2, np.int32).tofile(f)
+        f.write(np.array([B, N, poly, depth, has_from] + list(d2.shape), np.int32).tobytes())
+        f.write(np.array(list(lower) + [res, radius], np.float64).tobytes() + rows + np.ascontiguousarray(d2, np.int32).tobytes())
     subprocess.check_call([exe, "clear", fin, fout])
     with open(fout, "rb") as f:
         out = dict(status=np.fromfile(f, np.int32, B), verdict=np.fromfile(f, np.int32, B), where=np.fromfile(f, np.int32, B * 2).reshape(B, 2),

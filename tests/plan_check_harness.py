@@ -7,6 +7,8 @@ direct_cluster_plan_check_batch (include/direct_cluster.h, "plans against the re
                with a summed-area table of its own; it also checks the nesting of every visited parent / child pair, counts its
                box tests and times itself (for the bench tool).
   dyadic       the curve's points at the dyadic parameters of a depth, by the same halving: the soundness test's samples.
+  plan_rows / ROW_FRONT / row_section   the row front of the restatements (NumPy) and of the programs (C++, with the writer of
+               what it reads), each kept once here for tests/dist_field_harness.py too: validity, start times, control points.
 and the inputs the CPU and the GPU tests share."""
 import os
 import subprocess
@@ -93,31 +95,40 @@ def starts(Trow, n):
     return np.concatenate([[0.0], np.cumsum(np.asarray(Trow[:n], np.float64))])
 
 
-def restate(inp, grid, depth, margin=0.0, outside_blocks=False, use_t_from=True, lower=LOWER, res=RES):
-    """inp: dict(n_seg [B], T [B][N], bez or poly [B][N][18], t_from [B] or absent) -> dict of the call's outputs as they read in
-    HOST memory.  float32 inputs are promoted exactly, as the kernels do."""
+def plan_rows(inp, use_t_from=True):
+    """The front of both restatements (this one and dist_field_harness.restate_clearance).  inp: dict(n_seg [B], T [B][N], bez or
+    poly [B][N][18], t_from [B] or absent); float32 inputs are promoted exactly, as the kernels do.
+    -> (T [B][N] float64, t_from [B] or None, rows): rows[b] = (n_seg, whether the row is valid, and for a valid row its control
+    points in metres [n][3][6] and its start times S [n + 1])"""
     n_seg = np.asarray(inp["n_seg"], np.int32)
     T = np.asarray(inp["T"]).astype(np.float64)
     poly = inp.get("poly") is not None
     coef = np.asarray(inp["poly"] if poly else inp["bez"]).astype(np.float64)
     t_from = inp.get("t_from") if use_t_from else None
     B, N = T.shape
-    inv = 1.0 / res
-    lower = np.asarray(lower, np.float64)
-    out = dict(status=np.zeros(B, np.int32), verdict=np.zeros(B, np.int32), t_free=np.zeros(B), first=np.full((B, 2), -1, np.int32),
-               hit_box=np.full((B, 6), -1, np.int32), seg_first=np.full((B, N), -1, np.int32))
+    rows = []
     for b in range(B):
         n = int(n_seg[b])
         ok = 1 <= n <= N and bool(np.all(np.isfinite(T[b, :n]) & (T[b, :n] > 0)))
         ok = ok and not (t_from is not None and np.isnan(t_from[b]))
-        pts = []
-        if ok:
-            pts = [control_points(coef[b, i], T[b, i], poly) for i in range(n)]
-            ok = all(bool(np.all(np.abs(p) <= MAX_COORD)) for p in pts)  # False for NaN
+        pts = [control_points(coef[b, i], T[b, i], poly) for i in range(n)] if ok else []
+        ok = ok and all(bool(np.all(np.abs(p) <= MAX_COORD)) for p in pts)  # False for NaN
+        rows.append((n, ok, pts, starts(T[b], n) if ok else None))
+    return T, t_from, rows
+
+
+def restate(inp, grid, depth, margin=0.0, outside_blocks=False, use_t_from=True, lower=LOWER, res=RES):
+    """inp as plan_rows takes it -> dict of the call's outputs as they read in HOST memory"""
+    T, t_from, rows = plan_rows(inp, use_t_from)
+    B, N = T.shape
+    inv = 1.0 / res
+    lower = np.asarray(lower, np.float64)
+    out = dict(status=np.zeros(B, np.int32), verdict=np.zeros(B, np.int32), t_free=np.zeros(B), first=np.full((B, 2), -1, np.int32),
+               hit_box=np.full((B, 6), -1, np.int32), seg_first=np.full((B, N), -1, np.int32))
+    for b, (n, ok, pts, S) in enumerate(rows):
         if not ok:
             out["status"][b], out["verdict"][b] = -1, INVALID
             continue
-        S = starts(T[b], n)
         out["t_free"][b] = S[n]
         for i in range(n):
             L = leaves(pts[i], depth)
@@ -165,15 +176,60 @@ def voxel_bytes(points, grid, lower=LOWER, res=RES):
 
 # ---- the header's descent, compiled by g++ -----------------------------------------------------------------------------
 
+# The row front of this module's program and of dist_field_harness's: the row section of an input file (row_section() writes it),
+# per row its validity, start times and control points, and the grid fields both headers' Grids have.  The start-time rule is
+# stated here on its own (a sum left to right, every T > 0 and finite), NOT taken from traj_eval_math.h, which the kernels use.
+ROW_FRONT = r'''
+namespace pk = direct::plancheck;
+struct Rows {
+  int B, N, poly, has_from;
+  std::vector<int> n_seg;
+  std::vector<double> T, coef, t_from;
+};
+// int32 n_seg[B]; float64 T[B][N], coef[B][N][18], t_from[B] (when has_from)
+static bool read_rows(FILE* f, Rows& R) {
+  const size_t B = R.B, slots = B * R.N;
+  R.n_seg.resize(B); R.T.resize(slots); R.coef.resize(slots * 18); R.t_from.assign(B, 0.0);
+  return fread(R.n_seg.data(), 4, B, f) == B && fread(R.T.data(), 8, slots, f) == slots &&
+         fread(R.coef.data(), 8, slots * 18, f) == slots * 18 && (!R.has_from || fread(R.t_from.data(), 8, B, f) == B);
+}
+// whether row b is valid; then S[0 .. n] and the control points P[i * 18 ..] of its n segments
+static int row_front(const Rows& R, int b, std::vector<double>& S, std::vector<double>& P) {
+  const int n = R.n_seg[b];
+  const double* T = &R.T[(size_t)b * R.N];
+  int ok = 1 <= n && n <= R.N;
+  if (ok) {
+    S[0] = 0.0;
+    for (int i = 0; i < n; i++) {
+      ok &= (T[i] > 0.0 && T[i] <= 1.7976931348623157e308) ? 1 : 0;
+      S[i + 1] = S[i] + T[i];
+    }
+  }
+  if (R.has_from && R.t_from[b] != R.t_from[b]) ok = 0;
+  P.resize((size_t)(ok ? n : 0) * 18);  // reused from row to row: every entry a caller reads is written below
+  for (int i = 0; ok && i < n; i++) {
+    const double* c = &R.coef[((size_t)b * R.N + i) * 18];
+    ok &= R.poly ? pk::ctrl_from_poly(c, T[i], &P[i * 18]) : pk::ctrl_from_bez(c, T[i], &P[i * 18]);
+  }
+  return ok;
+}
+template <class Grid>
+static void grid_front(Grid& g, const double* lower, double res, int X, int Y, int Z) {
+  for (int a = 0; a < 3; a++) g.lower[a] = lower[a];
+  g.inv = 1.0 / res;
+  g.size[0] = X; g.size[1] = Y; g.size[2] = Z;
+}
+'''
+
 HARNESS = r'''
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 #include "plan_check_math.h"
-namespace pc = direct::plancheck;
-// in: int32 B, N, poly, D, outside, has_from, X, Y, Z, reps, pad, pad; float64 lower[3], res, margin; int32 n_seg[B];
-//     float64 T[B][N], coef[B][N][18], t_from[B] (when has_from); uint8 map[G]
+''' + ROW_FRONT + r'''
+// in: int32 B, N, poly, D, outside, has_from, X, Y, Z, reps, pad, pad; float64 lower[3], res, margin; the row section;
+//     uint8 map[G]
 // out: int32 status[B], verdict[B], first[B][2], hit_box[B][6], seg_first[B][N]; float64 t_free[B];
 //      int64 box tests, parent/child pairs, pairs not nested, 0; float64 ms (best of reps)
 int main(int argc, char** argv) {
@@ -182,22 +238,15 @@ int main(int argc, char** argv) {
   int h[12];
   double d[5];
   if (!f || fread(h, 4, 12, f) != 12 || fread(d, 8, 5, f) != 5) return 1;
-  const int B = h[0], N = h[1], poly = h[2], D = h[3], has_from = h[5], X = h[6], Y = h[7], Z = h[8], reps = h[9];
+  const int B = h[0], N = h[1], D = h[3], has_from = h[5], X = h[6], Y = h[7], Z = h[8], reps = h[9];
   const size_t G = (size_t)X * Y * Z;
-  std::vector<int> n_seg(B);
-  std::vector<double> T((size_t)B * N), coef((size_t)B * N * 18), t_from(B, 0.0);
+  Rows R = {B, N, h[2], has_from};
   std::vector<uint8_t> map(G);
-  if (fread(n_seg.data(), 4, B, f) != (size_t)B || fread(T.data(), 8, T.size(), f) != T.size() ||
-      fread(coef.data(), 8, coef.size(), f) != coef.size())
-    return 1;
-  if (has_from && fread(t_from.data(), 8, B, f) != (size_t)B) return 1;
-  if (fread(map.data(), 1, G, f) != G) return 1;
+  if (!read_rows(f, R) || fread(map.data(), 1, G, f) != G) return 1;
   fclose(f);
-  pc::Grid grid;
-  for (int a = 0; a < 3; a++) grid.lower[a] = d[a];
-  grid.inv = 1.0 / d[3];
+  pk::Grid grid;
+  grid_front(grid, d, d[3], X, Y, Z);
   grid.margin = d[4];
-  grid.size[0] = X; grid.size[1] = Y; grid.size[2] = Z;
   grid.outside_blocks = h[4];
   // obstacles in [0, x) x [0, y) x [0, z)
   const int sz = Z + 1, syz = (Y + 1) * sz;
@@ -216,9 +265,9 @@ int main(int argc, char** argv) {
                at(x0, y0, z0) > 0;
   };
   std::vector<int> status(B), verdict(B), first((size_t)B * 2), hit((size_t)B * 6), seg_first((size_t)B * N);
-  std::vector<double> t_free(B), S(N + 1);
+  std::vector<double> t_free(B), S(N + 1), P;
   long long extra[4] = {0, 0, 0, 0};
-  int path_k[pc::kMaxDepth + 1], path_box[pc::kMaxDepth + 1][6];
+  int path_k[pk::kMaxDepth + 1], path_box[pk::kMaxDepth + 1][6];
   auto visit = [&](int dd, int k, const int* lo, const int* hi, int) {
     if (dd > 0) {
       extra[1]++;
@@ -234,40 +283,26 @@ int main(int argc, char** argv) {
     extra[0] = extra[1] = extra[2] = 0;
     const auto c0 = std::chrono::steady_clock::now();
     for (int b = 0; b < B; b++) {
-      const int n = n_seg[b];
+      const int n = R.n_seg[b];
       for (int i = 0; i < N; i++) seg_first[(size_t)b * N + i] = -1;
       for (int q = 0; q < 2; q++) first[b * 2 + q] = -1;
       for (int q = 0; q < 6; q++) hit[b * 6 + q] = -1;
-      int ok = 1 <= n && n <= N;
-      if (ok) {
-        S[0] = 0.0;
-        for (int i = 0; i < n; i++) {
-          const double Ti = T[(size_t)b * N + i];
-          ok &= (Ti > 0.0 && Ti <= 1.7976931348623157e308) ? 1 : 0;
-          S[i + 1] = S[i] + Ti;
-        }
-      }
-      if (has_from && t_from[b] != t_from[b]) ok = 0;
-      std::vector<double> P((size_t)(ok ? n : 0) * 18);
-      for (int i = 0; ok && i < n; i++) {
-        const double* c = &coef[((size_t)b * N + i) * 18];
-        ok &= poly ? pc::ctrl_from_poly(c, T[(size_t)b * N + i], &P[i * 18]) : pc::ctrl_from_bez(c, T[(size_t)b * N + i], &P[i * 18]);
-      }
+      const int ok = row_front(R, b, S, P);
       status[b] = ok ? 0 : -1;
       verdict[b] = ok ? 0 : -1;
       t_free[b] = ok ? S[n] : 0.0;
       for (int i = 0; ok && i < n; i++) {
-        const double Ti = T[(size_t)b * N + i];
-        const int k = pc::descend(&P[i * 18], S[i], Ti, D, 0, 0, has_from, t_from[b], grid, occupied, visit, -1, &extra[0]);
+        const double Ti = R.T[(size_t)b * N + i];
+        const int k = pk::descend(&P[i * 18], S[i], Ti, D, 0, 0, has_from, R.t_from[b], grid, occupied, visit, -1, &extra[0]);
         seg_first[(size_t)b * N + i] = k;
         if (k >= 0 && first[b * 2] < 0) {
           double leaf[18];
           int lo[3], hi[3], blocked;
-          pc::derive(&P[i * 18], D, k, leaf);
-          verdict[b] = pc::judge(leaf, grid, occupied, lo, hi, &blocked);
+          pk::derive(&P[i * 18], D, k, leaf);
+          verdict[b] = pk::judge(leaf, grid, occupied, lo, hi, &blocked);
           first[b * 2] = i; first[b * 2 + 1] = k;
           for (int a = 0; a < 3; a++) { hit[b * 6 + a] = lo[a]; hit[b * 6 + 3 + a] = hi[a]; }
-          t_free[b] = pc::node_time(S[i], Ti, D, k);
+          t_free[b] = pk::node_time(S[i], Ti, D, k);
         }
       }
     }
@@ -299,24 +334,24 @@ def build(workdir):
     return str(workdir), exe
 
 
+def row_section(inp, use_t_from=True):
+    """-> ([B, N, poly, has_from], the bytes of the row section of a harness input file): what ROW_FRONT's read_rows reads"""
+    poly = inp.get("poly") is not None
+    T = np.asarray(inp["T"]).astype(np.float64)
+    t_from = inp.get("t_from") if use_t_from else None
+    parts = [np.asarray(inp["n_seg"], np.int32), T, np.asarray(inp["poly"] if poly else inp["bez"]).astype(np.float64)]
+    parts += [] if t_from is None else [np.asarray(t_from, np.float64)]
+    return list(T.shape) + [int(poly), int(t_from is not None)], b"".join(np.ascontiguousarray(a).tobytes() for a in parts)
+
+
 def run(harness, inp, grid, depth, margin=0.0, outside_blocks=False, use_t_from=True, lower=LOWER, res=RES, reps=1):
     """-> (outputs as restate() gives them, dict(tests, pairs, not_nested, ms)) of the header's descent"""
     d, exe = harness
-    poly = inp.get("poly") is not None
-    T = np.ascontiguousarray(np.asarray(inp["T"]).astype(np.float64))
-    coef = np.ascontiguousarray(np.asarray(inp["poly"] if poly else inp["bez"]).astype(np.float64))
-    t_from = inp.get("t_from") if use_t_from else None
-    B, N = T.shape
+    (B, N, poly, has_from), rows = row_section(inp, use_t_from)
     fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
     with open(fin, "wb") as f:
-        np.array([B, N, int(poly), depth, int(outside_blocks), int(t_from is not None)] + list(grid.shape) + [reps, 0, 0], np.int32).tofile(f)
-        np.array(list(lower) + [res, margin], np.float64).tofile(f)
-        np.ascontiguousarray(inp["n_seg"], np.int32).tofile(f)
-        T.tofile(f)
-        coef.tofile(f)
-        if t_from is not None:
-            np.ascontiguousarray(t_from, np.float64).tofile(f)
-        np.ascontiguousarray(grid, np.uint8).tofile(f)
+        f.write(np.array([B, N, poly, depth, int(outside_blocks), has_from] + list(grid.shape) + [reps, 0, 0], np.int32).tobytes())
+        f.write(np.array(list(lower) + [res, margin], np.float64).tobytes() + rows + np.ascontiguousarray(grid, np.uint8).tobytes())
     subprocess.check_call([exe, fin, fout])
     with open(fout, "rb") as f:
         out = dict(status=np.fromfile(f, np.int32, B), verdict=np.fromfile(f, np.int32, B), first=np.fromfile(f, np.int32, B * 2).reshape(B, 2),

@@ -142,13 +142,21 @@ def raw_call(g, inp, outs=OUTS, **change):
     return cluster._lib().direct_cluster_plan_check_batch(g.h, C.addressof(par), C.addressof(o)), arr, (par, T, coef, n_seg)
 
 
+NAN3, SOME = (C.c_double * 3)(0.0, float("nan"), 0.0), np.zeros(8)
+# every single fault with the words of its refusal, as direct_cluster_last_error() gives them
+FAULTS = [(dict(n_seg=None), b"null argument"), (dict(T=None), b"null argument"), (dict(batch=0), b"batch and n_seg_max must be positive"),
+          (dict(batch=-1), b"batch and n_seg_max must be positive"), (dict(n_seg_max=0), b"batch and n_seg_max must be positive"),
+          (dict(bez=None), b"exactly one of bez and poly"), (dict(poly=SOME.ctypes.data), b"exactly one of bez and poly"),
+          (dict(mem=2), b"neither DIRECT_MEM_HOST"), (dict(dtype=2), b"dtype is neither"), (dict(depth=-1), b"depth outside"),
+          (dict(depth=13), b"depth outside"), (dict(map_lower=NAN3), b"map_lower"), (dict(margin=-0.1), b"margin must be"),
+          (dict(margin=float("nan")), b"margin must be"), (dict(resolution=0.0), b"resolution must be"), (dict(resolution=-1.0), b"resolution must be"),
+          (dict(resolution=float("inf")), b"resolution must be"), (dict(resolution=float("nan")), b"resolution must be"),
+          (dict(outside_blocks=2), b"outside_blocks")]
+
+
 def test_invalid_arguments_launch_nothing(gen, inputs):
     inp = ph.pick(inputs["random7"], "bez")
-    nan3, some = (C.c_double * 3)(0.0, float("nan"), 0.0), np.zeros(8)
-    cases = [dict(n_seg=None), dict(T=None), dict(batch=0), dict(batch=-1), dict(n_seg_max=0), dict(bez=None), dict(poly=some.ctypes.data),
-             dict(mem=2), dict(dtype=2), dict(depth=-1), dict(depth=13), dict(map_lower=nan3), dict(margin=-0.1), dict(margin=float("nan")),
-             dict(resolution=0.0), dict(resolution=-1.0), dict(resolution=float("inf")), dict(resolution=float("nan")), dict(outside_blocks=2)]
-    for change in cases:
+    for change, _words in FAULTS:
         st, arr, _keep = raw_call(gen, inp, **change)
         assert st == abi.DIRECT_ERR_INVALID, change
         assert all((a == 77).all() for a in arr.values()), change
@@ -165,6 +173,27 @@ def test_invalid_arguments_launch_nothing(gen, inputs):
     arr["status"][:] = 77
     assert lib.direct_cluster_plan_check_batch(bare.h, C.addressof(par), C.addressof(o)) == abi.DIRECT_ERR_INVALID
     assert (arr["status"] == 77).all() and b"map" in lib.direct_cluster_last_error()
+    bare.close()
+
+
+def test_refusals_name_their_cause(gen, inputs):
+    """every single fault is refused in its own words, and of two faults the one the call tests first is named"""
+    inp = ph.pick(inputs["random7"], "bez")
+    last = cluster._lib().direct_cluster_last_error
+    for change, words in FAULTS:
+        st, _arr, _keep = raw_call(gen, inp, **change)
+        assert st == abi.DIRECT_ERR_INVALID and words in last(), (change, last())
+    pairs = [(dict(depth=13, resolution=0.0), b"depth outside"), (dict(outside_blocks=2, resolution=0.0), b"outside_blocks"),
+             (dict(resolution=0.0, margin=-1.0), b"resolution must be"), (dict(margin=-1.0, map_lower=NAN3), b"margin must be"),
+             (dict(mem=2, dtype=2), b"neither DIRECT_MEM_HOST")]
+    for change, words in pairs:
+        st, _arr, _keep = raw_call(gen, inp, **change)
+        assert st == abi.DIRECT_ERR_INVALID and words in last(), (change, last())
+    bare = cluster.ClusterGenerator(mh.DIMS, max_batch=2, cluster_capacity=64, candidate_capacity=64)   # a handle without a map
+    st, _arr, _keep = raw_call(bare, inp, depth=13)
+    assert st == abi.DIRECT_ERR_INVALID and b"depth outside" in last(), last()
+    st, _arr, _keep = raw_call(bare, inp)
+    assert st == abi.DIRECT_ERR_INVALID and b"the handle has no map" in last(), last()
     bare.close()
 
 
