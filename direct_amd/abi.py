@@ -150,6 +150,9 @@ class CubeCorridorOut(C.Structure):  # direct_cube_corridor_out_t (include/direc
 
 
 CUBE_CORRIDOR_OUTPUTS = ("n_seg", "n_planes", "planes", "seeds", "centers", "cube_idx", "rtn")   # the arrays of CubeCorridorOut
+# direct_cluster_cube_corridor_clear_batch(handle, CubeCorridorIn*, int32 min_d2, CubeCorridorOut*, int64 info[2] or NULL)
+CUBE_CORRIDOR_CLEAR_ARGTYPES = (C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p)
+CUBE_CORRIDOR_FLOOR_SLOTS = 2   # kFloorSlots of cube_corridor_clear_math.h: floor tables resident on a handle
 
 
 class GridPathClearIn(C.Structure):  # direct_grid_path_clear_in_t (include/direct_cluster.h)

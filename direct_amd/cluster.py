@@ -43,7 +43,8 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_set_stream", "direct_cluster_hull_planes_batch", "direct_cluster_grid_path_batch",
            "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
-           "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch")
+           "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch",
+           "direct_cluster_cube_corridor_clear_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -82,6 +83,7 @@ def _lib():
         L.direct_cluster_cube_corridor_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_grid_path_clear_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_grid_path_fan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_cube_corridor_clear_batch.argtypes = list(abi.CUBE_CORRIDOR_CLEAR_ARGTYPES)
         _BOUND = True
     return L
 
@@ -426,6 +428,26 @@ class ClusterGenerator:
         corridorInsertGeneration's from an empty corridor (False).  dtype: float64, or float32 as one rounding of it.
         -> dict(n_seg [B], n_planes [B][S], planes [B][S][p_max][4], seeds [B][S][3], centers [B][S][3], cube_idx [B][S][6], rtn [B]),
         S = seg_capacity; entries from a row's n_seg on are zero"""
+        return self._cube_corridors(_lib().direct_cluster_cube_corridor_batch, paths, path_len, map_lower, resolution, itr_inflate_max,
+                                    pop_back, seg_capacity, p_max, dtype)
+
+    def cube_corridors_clear(self, paths, path_len, map_lower, resolution, min_d2, itr_inflate_max=1000, pop_back=True, seg_capacity=64,
+                             p_max=6, dtype=np.float64):
+        """cube_corridors on the resident distance field (direct_cluster_cube_corridor_clear_batch): a cube stops at voxels whose
+        stored D2 is below min_d2 (voxel^2, the floor of grid_paths_clear / grid_paths_fan), so every voxel of a cube but its seed
+        has D2 >= min_d2.  min_d2 <= 1 is cube_corridors and needs no field; min_d2 >= 2 needs build_distance_field() after the
+        last change of the map and a floor not above the field's cap2.  Arguments, kinds and result as cube_corridors, plus
+        info [2] int64 (NumPy): info[0] 1 if the call built a floor table, 0 if it reused one (two stay resident, least recently
+        used replaced) or ran in neutral mode; info[1] the voxels below the floor."""
+        info = np.zeros(2, np.int64)
+        fn = _lib().direct_cluster_cube_corridor_clear_batch
+        out = self._cube_corridors(lambda h, par, o: fn(h, par, int(min_d2), o, info.ctypes.data), paths, path_len, map_lower, resolution,
+                                   itr_inflate_max, pop_back, seg_capacity, p_max, dtype)
+        out["info"] = info
+        return out
+
+    def _cube_corridors(self, call, paths, path_len, map_lower, resolution, itr_inflate_max, pop_back, seg_capacity, p_max, dtype):
+        """the two cube corridor calls: call(handle, address of the input struct, address of the output struct) -> status"""
         lower = np.asarray(map_lower, np.float64).reshape(3)
         f32 = np.dtype(dtype) == np.float32
         par = CubeCorridorIn(itr_inflate_max=int(itr_inflate_max), pop_back=int(bool(pop_back)), seg_capacity=int(seg_capacity),
@@ -455,7 +477,7 @@ class ClusterGenerator:
         out = dict(n_seg=z(B, np.int32), n_planes=z((B, S), np.int32), planes=z((B, S, P, 4), real), seeds=z((B, S, 3), real),
                    centers=z((B, S, 3), real), cube_idx=z((B, S, 6), np.int32), rtn=z(B, np.int32))
         o = CubeCorridorOut(mem, 0, *[ptr(out[k]) for k in abi.CUBE_CORRIDOR_OUTPUTS])
-        _check(_lib().direct_cluster_cube_corridor_batch(self.h, C.addressof(par), C.addressof(o)))
+        _check(call(self.h, C.addressof(par), C.addressof(o)))
         return out
 
     def set_stream(self, hip_stream):

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/direct_cluster.h"
+#include "cube_corridor_clear_math.h"
 #include "cube_corridor_math.h"
 #include "grid_path_clear_math.h"
 #include "grid_path_fan_math.h"
@@ -989,6 +990,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "dist_field.h"
 #include "plan_clear.h"
 #include "cube_corridor.h"
+#include "cube_corridor_clear.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1039,6 +1041,10 @@ struct direct_cluster_handle_s {
   hs::Block fan_ws;    // workspace of grid_path_fan_batch (goals, their grouping, bounds, one read-back ring or two per goal), grown on demand
   hs::Block fan_out;   // device staging of its host outputs, grown on demand
   int fan_bound_every = 1;  // rounds between two k_fan_bound launches: 1 or 8 (DIRECT_CLUSTER_FAN_BOUND_EVERY: experiments)
+  unsigned long long dist_serial = 0;  // successful direct_cluster_distance_field calls: the key of the floor tables below
+  int* floor_tab[cc::kFloorSlots] = {};        // floor tables of cube_corridor_clear_batch (layout of D.sat), allocated by its first clear-mode call
+  cc::FloorSlot floor_slot[cc::kFloorSlots] = {};  // what each holds
+  unsigned long long floor_clock = 0;  // ticks at every use of a slot: least recently used is the smallest FloorSlot::used
 };
 
 namespace {
@@ -1195,6 +1201,73 @@ hipError_t download_fields(direct_cluster_handle_t h, double* dist, size_t n, in
   if (e != hipSuccess || !dist) return e;
   return hipMemcpyAsync(dist, h->P.field, n * (size_t)h->P.G * sizeof(double),
                         mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
+}
+
+// cube_corridor_batch and cube_corridor_clear_batch.  What both refuse, in the plain call's order; DIRECT_OK: nothing to refuse.
+// `more` is a further refusal that the call's arguments alone decide (or null): it comes before what the handle holds.
+direct_status_t cube_corridor_refusal(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, const direct_cube_corridor_out_t* out,
+                                      const char* more) {
+  if (!h || !in || !out || !in->path_xyz || !in->path_len) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (in->batch <= 0 || in->path_capacity <= 0 || in->seg_capacity <= 0 || in->itr_inflate_max <= 0)
+    return cfail(DIRECT_ERR_INVALID, "batch, path_capacity, seg_capacity and itr_inflate_max must be positive");
+  if (in->p_max < cc::kPlanes) return cfail(DIRECT_ERR_INVALID, "p_max below 6");
+  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
+    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->plane_dtype != DIRECT_F32 && in->plane_dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "plane_dtype is neither DIRECT_F32 nor DIRECT_F64");
+  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
+  if (more) return cfail(DIRECT_ERR_INVALID, more);
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
+  if (slots >= (1ull << 28) || segs * (size_t)in->p_max >= (1ull << 28))
+    return cfail(DIRECT_ERR_UNSUPPORTED, "batch * path_capacity or batch * seg_capacity * p_max of 2^28 or more");
+  return DIRECT_OK;
+}
+// Their workspace, staging, launches and way back, after cube_corridor_refusal and hipSetDevice.  D is the handle's Dev, or a copy
+// whose `sat` is a floor table: the slab test counts what that table counts.  before() enqueues what the table still needs, behind
+// the first of the handle's two events; after() enqueues what else the call reads.  `who` opens the message of a device error.
+template <class Before, class After>
+direct_status_t cube_corridor_run(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out, const Dev& D,
+                                  const char* who, Before before, After after) {
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
+  const size_t w_stack = (slots * 6 * sizeof(int) + 255) & ~(size_t)255;
+  CHIP_TRY(hs::grow(h->cube_ws, h->stream, w_stack + slots * sizeof(int)));
+  CubeDev A = {};
+  A.batch = in->batch; A.path_cap = in->path_capacity; A.seg_cap = in->seg_capacity; A.p_max = in->p_max;
+  A.itr_inflate_max = in->itr_inflate_max; A.pop_back = in->pop_back ? 1 : 0;
+  A.res = in->resolution;
+  for (int a = 0; a < 3; a++) A.lower[a] = in->map_lower[a];
+  A.cube = (int*)h->cube_ws.p;
+  A.stack = (int*)((char*)h->cube_ws.p + w_stack);
+  const size_t r = in->plane_dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(out->mem == DIRECT_MEM_HOST);
+  hs::stage_in(si, &A.path_xyz, in->path_xyz, slots * 3 * sizeof(int32_t));
+  hs::stage_in(si, &A.path_len, in->path_len, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_seg, out->n_seg, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_planes, out->n_planes, segs * sizeof(int32_t));
+  hs::stage_out(so, &A.planes, out->planes, segs * (size_t)in->p_max * 4 * r);
+  hs::stage_out(so, &A.seeds, out->seeds, segs * 3 * r);
+  hs::stage_out(so, &A.centers, out->centers, segs * 3 * r);
+  hs::stage_out(so, &A.cube_idx, out->cube_idx, segs * 6 * sizeof(int32_t));
+  hs::stage_out(so, &A.rtn, out->rtn, B * sizeof(int32_t));
+  CHIP_TRY(hs::stage_upload(si, h->cube_in, h->stream));
+  CHIP_TRY(hs::stage_upload(so, h->cube_out, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = before();
+  if (e == hipSuccess) {
+    const int blocks = (int)std::min<size_t>((slots + 63) / 64, 8192);  // a fixed grid beyond 524288 slots: the lanes stride
+    hipLaunchKernelGGL(k_cube_inflate, dim3(blocks), dim3(64), 0, h->stream, D, A);
+    if (in->plane_dtype == DIRECT_F32) hipLaunchKernelGGL(k_cube_walk<float>, dim3(in->batch), dim3(64), 0, h->stream, A);
+    else hipLaunchKernelGGL(k_cube_walk<double>, dim3(in->batch), dim3(64), 0, h->stream, A);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::stage_download(so, h->stream, e);
+  if (e == hipSuccess) e = after();
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string(who) + hipGetErrorString(e));
+  return DIRECT_OK;
 }
 }  // namespace
 
@@ -1674,6 +1747,7 @@ direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: ") + hipGetErrorString(e));
   h->dist_valid = true;
   h->dist_cap2 = A.cap2;
+  h->dist_serial++;
   if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)(int32_t)(cnt[1] & 0xffffffffull); }
   return DIRECT_OK;
 }
@@ -1722,53 +1796,45 @@ direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, c
 }
 
 direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out) {
-  if (!h || !in || !out || !in->path_xyz || !in->path_len) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (in->batch <= 0 || in->path_capacity <= 0 || in->seg_capacity <= 0 || in->itr_inflate_max <= 0)
-    return cfail(DIRECT_ERR_INVALID, "batch, path_capacity, seg_capacity and itr_inflate_max must be positive");
-  if (in->p_max < cc::kPlanes) return cfail(DIRECT_ERR_INVALID, "p_max below 6");
-  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
-    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (in->plane_dtype != DIRECT_F32 && in->plane_dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "plane_dtype is neither DIRECT_F32 nor DIRECT_F64");
-  if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
-  for (int a = 0; a < 3; a++)
-    if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
-  if (slots >= (1ull << 28) || segs * (size_t)in->p_max >= (1ull << 28))
-    return cfail(DIRECT_ERR_UNSUPPORTED, "batch * path_capacity or batch * seg_capacity * p_max of 2^28 or more");
+  if (const direct_status_t rc = cube_corridor_refusal(h, in, out, nullptr)) return rc;
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  const Dev& D = h->D;
-  const size_t w_stack = (slots * 6 * sizeof(int) + 255) & ~(size_t)255;
-  CHIP_TRY(hs::grow(h->cube_ws, h->stream, w_stack + slots * sizeof(int)));
-  CubeDev A = {};
-  A.batch = in->batch; A.path_cap = in->path_capacity; A.seg_cap = in->seg_capacity; A.p_max = in->p_max;
-  A.itr_inflate_max = in->itr_inflate_max; A.pop_back = in->pop_back ? 1 : 0;
-  A.res = in->resolution;
-  for (int a = 0; a < 3; a++) A.lower[a] = in->map_lower[a];
-  A.cube = (int*)h->cube_ws.p;
-  A.stack = (int*)((char*)h->cube_ws.p + w_stack);
-  const size_t r = in->plane_dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
-  hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(out->mem == DIRECT_MEM_HOST);
-  hs::stage_in(si, &A.path_xyz, in->path_xyz, slots * 3 * sizeof(int32_t));
-  hs::stage_in(si, &A.path_len, in->path_len, B * sizeof(int32_t));
-  hs::stage_out(so, &A.n_seg, out->n_seg, B * sizeof(int32_t));
-  hs::stage_out(so, &A.n_planes, out->n_planes, segs * sizeof(int32_t));
-  hs::stage_out(so, &A.planes, out->planes, segs * (size_t)in->p_max * 4 * r);
-  hs::stage_out(so, &A.seeds, out->seeds, segs * 3 * r);
-  hs::stage_out(so, &A.centers, out->centers, segs * 3 * r);
-  hs::stage_out(so, &A.cube_idx, out->cube_idx, segs * 6 * sizeof(int32_t));
-  hs::stage_out(so, &A.rtn, out->rtn, B * sizeof(int32_t));
-  CHIP_TRY(hs::stage_upload(si, h->cube_in, h->stream));
-  CHIP_TRY(hs::stage_upload(so, h->cube_out, h->stream));
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  const int blocks = (int)std::min<size_t>((slots + 63) / 64, 8192);  // a fixed grid beyond 524288 slots: the lanes stride
-  hipLaunchKernelGGL(k_cube_inflate, dim3(blocks), dim3(64), 0, h->stream, D, A);
-  if (in->plane_dtype == DIRECT_F32) hipLaunchKernelGGL(k_cube_walk<float>, dim3(in->batch), dim3(64), 0, h->stream, A);
-  else hipLaunchKernelGGL(k_cube_walk<double>, dim3(in->batch), dim3(64), 0, h->stream, A);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("cube_corridor_batch: ") + hipGetErrorString(e));
+  return cube_corridor_run(h, in, out, h->D, "cube_corridor_batch: ", [] { return hipSuccess; }, [] { return hipSuccess; });
+}
+
+direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, int32_t min_d2,
+                                                         direct_cube_corridor_out_t* out, int64_t* info) {
+  if (const direct_status_t rc = cube_corridor_refusal(h, in, out, min_d2 < 0 ? "min_d2 must not be negative" : nullptr)) return rc;
+  const bool neutral = cc::floor_neutral(min_d2);  // the map's own table: the field is not looked at
+  if (!neutral)
+    if (const char* why = clear_field_refusal(h, min_d2, 0)) return cfail(DIRECT_ERR_INVALID, why);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  Dev D = h->D;
+  const size_t entries = (size_t)(D.max_x + 1) * D.sat_yz;
+  int slot = -1, hit = 1;
+  if (!neutral) {
+    if (!h->floor_tab[0]) {  // all or nothing
+      const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->floor_tab[0], entries * sizeof(int)), hs::want(&h->floor_tab[1], entries * sizeof(int))});
+      if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("cube_corridor_clear_batch: table allocation: ") + hipGetErrorString(ae));
+    }
+    slot = cc::floor_slot_choose(h->floor_slot, cc::kFloorSlots, min_d2, h->dist_serial, &hit);
+    D.sat = h->floor_tab[slot];
+    if (!hit) h->floor_slot[slot].valid = 0;  // until its build has drained without an error
+  }
+  int count = 0;  // the table's last entry is the sum over the whole map
+  const bool fetch = neutral ? info != nullptr : !hit;
+  const direct_status_t rc = cube_corridor_run(h, in, out, D, "cube_corridor_clear_batch: ", [&] {
+    if (hit) return hipSuccess;
+    hipLaunchKernelGGL(k_floor_fill, dim3((unsigned)std::min<size_t>((entries + 255) / 256, 1024)), dim3(256), 0, h->stream, D, h->dist[0], min_d2);
+    for (int axis = 2; axis >= 0; axis--) hipLaunchKernelGGL(k_sat_scan, dim3(256), dim3(256), 0, h->stream, D, axis);
+    return hipGetLastError();
+  }, [&] { return fetch ? hipMemcpyAsync(&count, D.sat + (entries - 1), sizeof(int), hipMemcpyDeviceToHost, h->stream) : hipSuccess; });
+  if (rc != DIRECT_OK) return rc;
+  if (!neutral) {
+    cc::FloorSlot& s = h->floor_slot[slot];
+    if (!hit) { s.min_d2 = min_d2; s.serial = h->dist_serial; s.count = count; s.valid = 1; }
+    s.used = ++h->floor_clock;
+  }
+  if (info) { info[0] = hit ? 0 : 1; info[1] = neutral ? count : h->floor_slot[slot].count; }
   return DIRECT_OK;
 }
 

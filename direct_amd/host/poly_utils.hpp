@@ -17,6 +17,8 @@
 //     corridors.
 //   * cubeCorridorBatch(gridPaths, corridors, pop_back) the corridors of is_cluster_on == false (every polytope the inflated
 //     cube of its seed voxel) for many paths in ONE device call, direct_cluster_cube_corridor_batch: no rounds at all
+//   * cubeCorridorClearBatch(gridPaths, corridors, min_d2, pop_back) the same on the resident distance field: cubes stop at voxels
+//     closer to an obstacle than the floor (direct_cluster_cube_corridor_clear_batch)
 // Corridor / Polytope types are template parameters read through the member names of
 // global_planner/include/global_planner/utils/data_type.h:124-245 (polyhedrons, planes, center, seed_coord,
 // appendPlane, setSeed / setCenter where they exist); direct::PlainCorridor of ddp_optimizer.hpp fits.
@@ -233,6 +235,32 @@ class polyhedronGenerator {
   template <class Corridor>
   std::vector<bool> cubeCorridorBatch(const std::vector<std::vector<std::array<double, 3>>>& gridPaths,
                                       const std::vector<Corridor*>& corridors, bool pop_back = true) {
+    return cubeCorridors(gridPaths, corridors, pop_back, [this](const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out) {
+      return direct_cluster_cube_corridor_batch(h_, in, out);
+    });
+  }
+
+  // cubeCorridorBatch on the distance field the generator holds (buildDistanceField after the last change of the map;
+  // direct_cluster_cube_corridor_clear_batch): a cube stops at voxels whose stored D2 is below min_d2 (voxel^2, the floor of the
+  // clearance-aware path calls), so every voxel of a cube but its seed has D2 >= min_d2.  min_d2 <= 1 is cubeCorridorBatch and
+  // needs no field.  Fills corridors[p] the same way; lastTableBuilt() says whether the call built a floor table.
+  template <class Corridor>
+  std::vector<bool> cubeCorridorClearBatch(const std::vector<std::vector<std::array<double, 3>>>& gridPaths,
+                                           const std::vector<Corridor*>& corridors, int32_t min_d2, bool pop_back = true) {
+    return cubeCorridors(gridPaths, corridors, pop_back, [this, min_d2](const direct_cube_corridor_in_t* in, direct_cube_corridor_out_t* out) {
+      int64_t info[2] = {0, 0};
+      const direct_status_t st = direct_cluster_cube_corridor_clear_batch(h_, in, min_d2, out, info);
+      table_built_ = st == DIRECT_OK && info[0] == 1;
+      return st;
+    });
+  }
+  bool lastTableBuilt() const { return table_built_; }
+
+ private:
+  // The two cube corridor calls: call(in, out) is the device call.
+  template <class Corridor, class Call>
+  std::vector<bool> cubeCorridors(const std::vector<std::vector<std::array<double, 3>>>& gridPaths, const std::vector<Corridor*>& corridors,
+                                  bool pop_back, Call call) {
     if (!has_map_) throw std::runtime_error("polyhedronGenerator: no map");
     const size_t np = gridPaths.size();
     std::vector<bool> ok(np, false);
@@ -259,7 +287,7 @@ class polyhedronGenerator {
     direct_cube_corridor_out_t out{};
     out.mem = DIRECT_MEM_HOST; out.n_seg = n_seg.data(); out.planes = planes.data(); out.seeds = seeds.data();
     out.centers = centers.data(); out.rtn = rtn.data();
-    if (direct_cluster_cube_corridor_batch(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    if (call(&in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
     rounds_ = 1;
     polytopes_ = 0;
     for (size_t p = 0; p < np; p++) {
@@ -284,7 +312,6 @@ class polyhedronGenerator {
     return ok;
   }
 
- private:
   // The walk all entry points share.  pop_back: corridorGeneration's return into the last but one polytope (:524-528);
   // corridorInsertGeneration has none.
   template <class Corridor>
@@ -388,7 +415,7 @@ class polyhedronGenerator {
   std::array<double, 3> lower_;
   int mx_, my_, mz_, itr_inflate_, itr_cluster_, max_batch_;
   direct_cluster_handle_t h_ = nullptr;
-  bool has_map_ = false;
+  bool has_map_ = false, table_built_ = false;
   int rounds_ = 0, polytopes_ = 0;
 };
 

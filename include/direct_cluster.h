@@ -487,6 +487,42 @@ typedef struct {
 direct_status_t direct_cluster_cube_corridor_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in,
                                                    direct_cube_corridor_out_t* out);
 
+/* ---- radius-aware cube corridors: the corridor stage on the resident distance field (no reference counterpart) -----------
+ * direct_cluster_cube_corridor_batch with ONE change: a cube stops growing at voxels that are closer to an obstacle than a
+ * floor, not only at occupied ones.  It honours the floor of direct_cluster_grid_path_clear_batch / _fan_batch in the same
+ * units and with the same refusals, so that path, corridor and direct_cluster_plan_clearance_batch agree on one radius on one
+ * map.  Let D2[v] be the STORED field value of voxel v (direct_cluster_distance_field), in voxel^2 units; a voxel is BELOW THE
+ * FLOOR when D2[v] < min_d2.  D2 is 0 exactly on bytes == 1, so occupied voxels are below every floor >= 1.
+ *   Cube     the plain call's, with obstacles(box) = the number of voxels of the box below the floor.  Round order, border
+ *            rule, stop rule and itr_inflate_max are unchanged.  The seed voxel's own D2 is never looked at (as the start's D2
+ *            in the path calls): a vehicle closer to a wall than the floor still gets a polytope to start in.
+ *   Planes, centre, walk, output layouts and the per-row codes DIRECT_CUBE_CORRIDOR_* are the plain call's; both structs are
+ *            reused unchanged.
+ *   Neutral  min_d2 <= 1 uses the map's own table and returns the plain call's bytes.  No distance field is needed, and a
+ *            stale or missing one is not looked at (the neutral rule of the path calls).
+ *   Clear    min_d2 >= 2 reads a FLOOR TABLE: the summed-area table of "below the floor", in the layout of the map's table.
+ *            The handle keeps two of them, keyed by (min_d2, the field they were built from): a call whose key is resident
+ *            builds nothing, any other call builds into the slot used least recently, so two vehicle sizes alternating on one
+ *            map never rebuild.  Every successful direct_cluster_distance_field makes the resident tables stale.
+ * Equivalence: the result is, bit for bit, the plain call's on the map whose byte is (D2 < min_d2) ? 1 : 0.
+ * WHAT IT GUARANTEES (a derivation, not a measurement; the counterpart of plan_clearance's K).  Every voxel of every cube other
+ * than its seed voxel has stored D2 >= min_d2.  A polytope is contained in the union of its cube's voxel cubes (the half-voxel
+ * inflation of the planes; the voxels' corners when the cube is degenerate).  A point of a voxel is at most sqrt(3)/2 voxels
+ * from its centre, and an occupied voxel cube reaches at most sqrt(3)/2 voxels from its centre.  So every point of a polytope
+ * whose seed voxel also satisfies the floor is at least (sqrt(min_d2) - sqrt(3)) * resolution from every occupied voxel cube.
+ * On a field built with a cap, stored values at cap2 mean "at least cap2" and the floor may not exceed it.
+ * info (HOST, [2] or NULL): info[0] = 1 if this call built a table, 0 if it reused one or ran in neutral mode; info[1] = the
+ * number of voxels the table in use counts (neutral mode: the occupied voxels).
+ * DIRECT_ERR_INVALID, nothing launched: everything the plain call refuses; min_d2 < 0; and for min_d2 >= 2 a handle whose
+ * distance field is missing or older than its map (never a silent rebuild), or min_d2 above the cap2 the field was built with.
+ * DIRECT_ERR_UNSUPPORTED as the plain call.  Runs on the handle's stream and synchronises before it returns;
+ * direct_cluster_last_ms covers the table build, when there is one, and the two kernels.  The two tables (the size of the
+ * map's table each) are allocated together by the first clear-mode call, not by direct_cluster_create, and freed in
+ * direct_cluster_destroy.  The call leaves the map and its table, the field, resident clusters and every other workspace alone;
+ * it shares the plain call's workspace and staging blocks. */
+direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, int32_t min_d2,
+                                                         direct_cube_corridor_out_t* out, int64_t* info /* HOST [2] or NULL */);
+
 /* ---- clearance-aware grid paths: the path stage on the resident distance field (no reference counterpart) ------------
  * direct_cluster_grid_path_batch with two additions read from the distance field the handle holds: a hard floor ("never
  * closer than this") and a soft cost ("prefer open space, pay for proximity").  Optimal paths on a voxel graph hug corners
