@@ -183,6 +183,17 @@ class GridPathFanOut(C.Structure):  # direct_grid_path_fan_out_t (include/direct
 GRID_PATH_FAN_OUTPUTS = ("path_xyz", "path_len", "path_cost", "rtn", "path_d2", "path_min_d2", "dist", "stats")   # the arrays of GridPathFanOut
 
 
+class ReachableIn(C.Structure):  # direct_reachable_in_t (include/direct_cluster.h)
+    _fields_ = [("n", C.c_int64), ("mem_in", C.c_int32), ("min_d2", C.c_int32), ("starts", C.c_void_p), ("goals", C.c_void_p)]
+
+
+class ReachableOut(C.Structure):  # direct_reachable_out_t (include/direct_cluster.h)
+    _fields_ = [("mem", C.c_int32), ("reserved", C.c_int32), ("rtn", C.c_void_p), ("goal_label", C.c_void_p), ("goal_size", C.c_void_p)]
+
+
+REACHABLE_OUTPUTS = ("rtn", "goal_label", "goal_size")   # the arrays of ReachableOut
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

@@ -36,6 +36,7 @@ PlanClearIn, PlanClearOut = abi.PlanClearIn, abi.PlanClearOut  # direct_plan_cle
 CubeCorridorIn, CubeCorridorOut = abi.CubeCorridorIn, abi.CubeCorridorOut  # direct_cube_corridor_in_t, direct_cube_corridor_out_t
 GridPathClearIn, GridPathClearOut = abi.GridPathClearIn, abi.GridPathClearOut  # direct_grid_path_clear_in_t, direct_grid_path_clear_out_t
 GridPathFanIn, GridPathFanOut = abi.GridPathFanIn, abi.GridPathFanOut  # direct_grid_path_fan_in_t, direct_grid_path_fan_out_t
+ReachableIn, ReachableOut = abi.ReachableIn, abi.ReachableOut  # direct_reachable_in_t, direct_reachable_out_t
 
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
@@ -44,7 +45,8 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_map_from_cloud", "direct_cluster_get_map", "direct_cluster_plan_check_batch",
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
            "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch",
-           "direct_cluster_cube_corridor_clear_batch")
+           "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
+           "direct_cluster_reachable_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -84,6 +86,9 @@ def _lib():
         L.direct_cluster_grid_path_clear_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_grid_path_fan_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_cube_corridor_clear_batch.argtypes = list(abi.CUBE_CORRIDOR_CLEAR_ARGTYPES)
+        L.direct_cluster_free_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_get_free_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_reachable_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -479,6 +484,69 @@ class ClusterGenerator:
         o = CubeCorridorOut(mem, 0, *[ptr(out[k]) for k in abi.CUBE_CORRIDOR_OUTPUTS])
         _check(call(self.h, C.addressof(par), C.addressof(o)))
         return out
+
+    def build_free_components(self, min_d2=0):
+        """The 26-connected components of the enterable voxels of the map the handle holds now (direct_cluster_free_components):
+        a voxel is enterable when its byte is 0 and, for min_d2 > 1, its stored D2 is at least min_d2 (build_distance_field must
+        then have run since the map last changed) - the graph grid_paths / grid_paths_clear / grid_paths_fan move on.  Labels and
+        sizes stay resident on the handle until the map (or, with a floor, the field) changes.
+        -> dict(enterable, components, largest: size of the largest component, largest_label: its label or -1)"""
+        stats = np.zeros(4, np.int64)
+        _check(_lib().direct_cluster_free_components(self.h, int(min_d2), stats.ctypes.data))
+        return dict(enterable=int(stats[0]), components=int(stats[1]), largest=int(stats[2]), largest_label=int(stats[3]))
+
+    def free_components(self, mem="host"):
+        """-> (label, size), int32 of shape dims (direct_cluster_get_free_components): label is -1 on a voxel that is not enterable,
+        else the smallest linear index of its component; size the component's voxel count, else 0.  mem="device": tensors."""
+        assert mem in ("host", "device")
+        if mem == "host":
+            label, size = np.zeros(self.dims, np.int32), np.zeros(self.dims, np.int32)
+            _check(_lib().direct_cluster_get_free_components(self.h, abi.MEM_HOST, label.ctypes.data, size.ctypes.data, None))
+            return label, size
+        import torch
+        label, size = (torch.zeros(self.dims, dtype=torch.int32, device="cuda:%d" % self.device) for _ in range(2))
+        torch.cuda.current_stream(label.device).synchronize()  # the handle's stream is not torch's
+        _check(_lib().direct_cluster_get_free_components(self.h, abi.MEM_DEVICE, label.data_ptr(), size.data_ptr(), None))
+        return label, size
+
+    def free_components_floor(self):
+        """the normal form (<= 1 -> 0) of the min_d2 the resident labels were built with"""
+        v = C.c_int32(-1)
+        _check(_lib().direct_cluster_get_free_components(self.h, abi.MEM_HOST, None, None, C.addressof(v)))
+        return v.value
+
+    def reachable(self, starts, goals, min_d2=0, mem="host"):
+        """Which code grid_paths / grid_paths_clear / grid_paths_fan would return for each (start, goal) pair, from the resident
+        labels alone (direct_cluster_reachable_batch): GRID_PATH_OK (an OVERFLOW there is OK here), GRID_PATH_NO_PATH or
+        GRID_PATH_BAD_ENDPOINT.  starts, goals [n][3] int32, n unlimited: NumPy arrays or device tensors (one kind for both);
+        min_d2 must be the floor build_free_components ran with.  mem: where the outputs go ("host": NumPy, "device": tensors).
+        -> (rtn [n], goal_label [n], goal_size [n]): the goal's component and its voxel count, -1 and 0 for a goal that is
+        outside the map or not enterable - to drop goals in pockets too small to matter."""
+        assert mem in ("host", "device")
+        if isinstance(starts, np.ndarray) or not hasattr(starts, "data_ptr"):
+            starts = np.ascontiguousarray(starts, np.int32).reshape(-1, 3)
+            goals = np.ascontiguousarray(goals, np.int32).reshape(-1, 3)
+            mem_in, ps, pg = abi.MEM_HOST, starts.ctypes.data, goals.ctypes.data
+        else:
+            import torch
+            starts, goals = starts.to(torch.int32).contiguous().reshape(-1, 3), goals.to(torch.int32).contiguous().reshape(-1, 3)
+            assert starts.is_cuda and goals.is_cuda
+            torch.cuda.current_stream(starts.device).synchronize()  # the handle's stream is not torch's
+            mem_in, ps, pg = abi.MEM_DEVICE, starts.data_ptr(), goals.data_ptr()
+        assert tuple(starts.shape) == tuple(goals.shape)
+        n = int(starts.shape[0])
+        if mem == "host":
+            out = [np.zeros(n, np.int32) for _ in abi.REACHABLE_OUTPUTS]
+            ptrs = [a.ctypes.data for a in out]
+        else:
+            import torch
+            out = [torch.zeros(n, dtype=torch.int32, device="cuda:%d" % self.device) for _ in abi.REACHABLE_OUTPUTS]
+            torch.cuda.current_stream(out[0].device).synchronize()
+            ptrs = [a.data_ptr() for a in out]
+        par = ReachableIn(n=n, mem_in=mem_in, min_d2=int(min_d2), starts=ps, goals=pg)
+        o = ReachableOut(abi.MEM_HOST if mem == "host" else abi.MEM_DEVICE, 0, *ptrs)
+        _check(_lib().direct_cluster_reachable_batch(self.h, C.addressof(par), C.addressof(o)))
+        return tuple(out)
 
     def set_stream(self, hip_stream):
         _check(_lib().direct_cluster_set_stream(self.h, C.c_void_p(hip_stream)))

@@ -31,6 +31,7 @@
 #include "../../include/direct_cluster.h"
 #include "cube_corridor_clear_math.h"
 #include "cube_corridor_math.h"
+#include "free_comp_math.h"
 #include "grid_path_clear_math.h"
 #include "grid_path_fan_math.h"
 #include "grid_path_math.h"
@@ -991,6 +992,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "plan_clear.h"
 #include "cube_corridor.h"
 #include "cube_corridor_clear.h"
+#include "free_comp.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1045,6 +1047,11 @@ struct direct_cluster_handle_s {
   int* floor_tab[cc::kFloorSlots] = {};        // floor tables of cube_corridor_clear_batch (layout of D.sat), allocated by its first clear-mode call
   cc::FloorSlot floor_slot[cc::kFloorSlots] = {};  // what each holds
   unsigned long long floor_clock = 0;  // ticks at every use of a slot: least recently used is the smallest FloorSlot::used
+  int32_t *comp_label = nullptr, *comp_size = nullptr;  // labels and sizes of free_components, allocated by its first call
+  unsigned long long* comp_cnt = nullptr;  // [4] the counters behind its stats and its error word
+  fc::Key comp_key = {};                   // what the resident labels were built from (valid == 0: none)
+  unsigned long long map_gen = 0, field_gen = 0;  // calls that set the map / built a field so far: the labels' staleness key
+  hs::Block reach_in, reach_out;  // device staging of reachable_batch's host inputs / host outputs, grown on demand
 };
 
 namespace {
@@ -1179,6 +1186,9 @@ direct_status_t plan_run(direct_cluster_handle_t h, const hs::Stage& st, const c
   e = hs::drain(h->stream, e);
   return e == hipSuccess ? DIRECT_OK : cfail(DIRECT_ERR_DEVICE, std::string(who) + hipGetErrorString(e));
 }
+
+// what the fetch and reachable_batch say to a label set that is missing or older than the map (or, built with a floor, the field)
+const char* const kCompStale = "no valid free components: call direct_cluster_free_components after the map or the distance field changes";
 
 PathClearDev clear_dev(direct_cluster_handle_t h, int32_t min_d2, int32_t n_penalty) {
   PathClearDev C = {};
@@ -1342,7 +1352,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
-                       &h->cube_out, &h->fan_ws, &h->fan_out})
+                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out})
     hs::release(*b);
   hs::destroy(h->ev);
   delete h;
@@ -1352,6 +1362,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
 direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, const uint8_t* map_data) {
   if (!h || !map_data) return cfail(DIRECT_ERR_INVALID, "null argument");
   h->dist_valid = false;  // the map is about to change: a distance field no longer describes it
+  h->map_gen++;           // nor do the labels of free_components
   CHIP_TRY(hipSetDevice(h->cfg.device));
   CHIP_TRY(hipMemcpyAsync(h->map, map_data, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                           h->stream));
@@ -1366,6 +1377,7 @@ direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const d
                                               const float* xyz, int64_t* stats) {
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
   h->dist_valid = false;  // whether or not the call succeeds: a distance field is rebuilt by its caller
+  h->map_gen++;           // and so are the labels of free_components
   if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
   if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
   if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
@@ -1722,6 +1734,7 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
 
 direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t cap_vox, int64_t* stats) {
   if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  h->field_gen++;  // every call: labels of free_components built with a floor no longer count as describing the field
   if (cap_vox < 0 || cap_vox > df::kMaxCap) return cfail(DIRECT_ERR_INVALID, "cap_vox outside [0, 1024]");
   if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
   CHIP_TRY(hipSetDevice(h->cfg.device));
@@ -1984,6 +1997,87 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   e = hs::drain(h->stream, download_fields(h, out->dist, ns, in->mem, hs::stage_download(so, h->stream, e)));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_free_components(direct_cluster_handle_t h, int32_t min_d2, int64_t* stats) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  const int32_t floor = fc::normal_floor(min_d2);
+  if (floor)
+    if (const char* why = clear_field_refusal(h, floor, 0)) return cfail(DIRECT_ERR_INVALID, why);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  if (!h->comp_label) {  // all or nothing
+    const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->comp_label, (size_t)D.G * sizeof(int32_t)), hs::want(&h->comp_size, (size_t)D.G * sizeof(int32_t)),
+                                                    hs::want(&h->comp_cnt, 4 * sizeof(unsigned long long))});
+    if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("free_components: allocation: ") + hipGetErrorString(ae));
+  }
+  h->comp_key.valid = 0;
+  CompDev A = {};
+  A.map = h->map; A.d2 = floor ? h->dist[0] : nullptr; A.label = h->comp_label; A.size = h->comp_size; A.cnt = h->comp_cnt;
+  A.X = D.max_x; A.Y = D.max_y; A.Z = D.max_z; A.G = D.G; A.min_d2 = floor;
+  A.tx = gp::tiles_along(A.X); A.ty = gp::tiles_along(A.Y); A.tz = gp::tiles_along(A.Z);
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(h->comp_cnt, 0, 4 * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->comp_size, 0, (size_t)D.G * sizeof(int32_t), h->stream);
+  if (e == hipSuccess) e = free_comp_launch(A, h->stream);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt, h->comp_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("free_components: ") + hipGetErrorString(e));
+  if (cnt[3]) return cfail(DIRECT_ERR_DEVICE, "free_components: a union-find loop passed its trip bound (error word " + std::to_string(cnt[3]) + ")");
+  h->comp_key = fc::Key{h->map_gen, h->field_gen, floor, 1};
+  if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)cnt[1]; stats[2] = fc::stat_size(cnt[2]); stats[3] = fc::stat_label(cnt[2]); }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_free_components(direct_cluster_handle_t h, int32_t mem, int32_t* label, int32_t* size, int32_t* min_d2_built) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!fc::key_serves(h->comp_key, h->map_gen, h->field_gen)) return cfail(DIRECT_ERR_INVALID, kCompStale);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const hipMemcpyKind kind = mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (label) CHIP_TRY(hipMemcpyAsync(label, h->comp_label, (size_t)h->D.G * sizeof(int32_t), kind, h->stream));
+  if (size) CHIP_TRY(hipMemcpyAsync(size, h->comp_size, (size_t)h->D.G * sizeof(int32_t), kind, h->stream));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
+  if (min_d2_built) *min_d2_built = h->comp_key.floor;
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_reachable_batch(direct_cluster_handle_t h, const direct_reachable_in_t* in, direct_reachable_out_t* out) {
+  if (!h || !in || !out || !in->starts || !in->goals) return cfail(DIRECT_ERR_INVALID, "null argument");
+  // what the arguments alone decide comes first, then what the handle holds
+  if (in->n <= 0) return cfail(DIRECT_ERR_INVALID, "n must be positive");
+  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
+    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
+  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!fc::key_serves(h->comp_key, h->map_gen, h->field_gen)) return cfail(DIRECT_ERR_INVALID, kCompStale);
+  if (fc::normal_floor(in->min_d2) != h->comp_key.floor)
+    return cfail(DIRECT_ERR_INVALID, "min_d2 differs from the floor the free components were built with");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t n = (size_t)in->n;
+  ReachDev R = {};
+  R.label = h->comp_label; R.size = h->comp_size; R.n = in->n;
+  R.X = h->D.max_x; R.Y = h->D.max_y; R.Z = h->D.max_z;
+  hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(out->mem == DIRECT_MEM_HOST);
+  hs::stage_in(si, &R.starts, in->starts, n * 3 * sizeof(int32_t));
+  hs::stage_in(si, &R.goals, in->goals, n * 3 * sizeof(int32_t));
+  hs::stage_out(so, &R.rtn, out->rtn, n * sizeof(int32_t));
+  hs::stage_out(so, &R.goal_label, out->goal_label, n * sizeof(int32_t));
+  hs::stage_out(so, &R.goal_size, out->goal_size, n * sizeof(int32_t));
+  CHIP_TRY(hs::stage_upload(si, h->reach_in, h->stream));
+  CHIP_TRY(hs::stage_upload(so, h->reach_out, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipLaunchKernelGGL(k_reach, dim3((unsigned)std::min<size_t>((n + 255) / 256, kCcBlocks)), dim3(256), 0, h->stream, R);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("reachable_batch: ") + hipGetErrorString(e));
   return DIRECT_OK;
 }
 

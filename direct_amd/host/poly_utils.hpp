@@ -19,6 +19,8 @@
 //     cube of its seed voxel) for many paths in ONE device call, direct_cluster_cube_corridor_batch: no rounds at all
 //   * cubeCorridorClearBatch(gridPaths, corridors, min_d2, pop_back) the same on the resident distance field: cubes stop at voxels
 //     closer to an obstacle than the floor (direct_cluster_cube_corridor_clear_batch)
+//   * buildFreeComponents(min_d2) / reachable(starts, goals) which goals can be reached at all, before any path call runs
+//     (direct_cluster_free_components, direct_cluster_reachable_batch)
 // Corridor / Polytope types are template parameters read through the member names of
 // global_planner/include/global_planner/utils/data_type.h:124-245 (polyhedrons, planes, center, seed_coord,
 // appendPlane, setSeed / setCenter where they exist); direct::PlainCorridor of ddp_optimizer.hpp fits.
@@ -118,6 +120,42 @@ class polyhedronGenerator {
     int64_t stats[2] = {0, -1};
     if (direct_cluster_distance_field(h_, cap_vox, stats) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
     return (long long)stats[0];
+  }
+
+  // The 26-connected components of the enterable voxels of the map the generator holds NOW (direct_cluster_free_components):
+  // byte 0 and, for min_d2 > 1, stored D2 >= min_d2 (buildDistanceField after the last change of the map).  Resident until the
+  // map - with a floor also the field - changes: call it before reachable.
+  struct FreeComponents {
+    long long enterable = 0, components = 0, largest = 0, largest_label = -1;
+  };
+  FreeComponents buildFreeComponents(int min_d2 = 0) {
+    int64_t stats[4] = {0, 0, 0, -1};
+    if (direct_cluster_free_components(h_, min_d2, stats) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    comp_min_d2_ = min_d2;
+    FreeComponents c;
+    c.enterable = stats[0]; c.components = stats[1]; c.largest = stats[2]; c.largest_label = stats[3];
+    return c;
+  }
+  // Which code the path calls would return for each pair (direct_cluster_reachable_batch), coordinates through coord2Index:
+  // DIRECT_GRID_PATH_OK, _NO_PATH or _BAD_ENDPOINT (coord2Index clamps, so the last cannot occur), from the labels of the last
+  // buildFreeComponents and with its floor.  goal_size (may be null): the voxel count of each goal's component, 0 for a goal that
+  // is not enterable - to drop goals in pockets too small to matter before the path calls run.
+  std::vector<int32_t> reachable(const std::vector<std::array<double, 3>>& starts, const std::vector<std::array<double, 3>>& goals,
+                                 std::vector<int32_t>* goal_size = nullptr) {
+    if (starts.size() != goals.size() || starts.empty()) throw std::runtime_error("reachable: starts and goals must pair up");
+    const size_t n = starts.size();
+    std::vector<int32_t> s(n * 3), g(n * 3), rtn(n);
+    for (size_t i = 0; i < n; i++) {
+      const std::array<int, 3> a = coord2Index(starts[i]), b = coord2Index(goals[i]);
+      for (int k = 0; k < 3; k++) { s[3 * i + k] = a[k]; g[3 * i + k] = b[k]; }
+    }
+    if (goal_size) goal_size->assign(n, 0);
+    direct_reachable_in_t in{};
+    in.n = (int64_t)n; in.mem_in = DIRECT_MEM_HOST; in.min_d2 = comp_min_d2_; in.starts = s.data(); in.goals = g.data();
+    direct_reachable_out_t out{};
+    out.mem = DIRECT_MEM_HOST; out.rtn = rtn.data(); out.goal_size = goal_size ? goal_size->data() : nullptr;
+    if (direct_cluster_reachable_batch(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return rtn;
   }
 
   // One plan's certified distance to the occupied voxels (direct_cluster_plan_clearance_batch), arguments as checkTrajectory's.
@@ -417,6 +455,7 @@ class polyhedronGenerator {
   direct_cluster_handle_t h_ = nullptr;
   bool has_map_ = false, table_built_ = false;
   int rounds_ = 0, polytopes_ = 0;
+  int comp_min_d2_ = 0;  // the floor of the last buildFreeComponents
 };
 
 }  // namespace direct

@@ -663,13 +663,82 @@ typedef struct {
 direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, const direct_grid_path_fan_in_t* in,
                                                    direct_grid_path_fan_out_t* out);
 
+/* ---- free-space components and batched reachability (no reference counterpart) ----------------------------------------
+ * Which goals can be reached at all.  A pairwise path query whose goal is enterable but not connected ends with NO_PATH only
+ * after its relaxation has flooded the start's whole component, and in the fan one such goal switches pruning off for its
+ * group.  Connectivity is a pure function of the map and the floor, and it is undirected, because a move needs only the voxel it
+ * enters to be enterable: it is built once, kept resident and goes stale with the map, as the distance field does.
+ *   Enterable     enterable(v) = map byte of v == 0 && (min_d2 <= 1 || D2[v] >= min_d2), D2 the STORED distance field: word for
+ *                 word the "a move goes INTO" rule of direct_cluster_grid_path_batch (min_d2 <= 1) and
+ *                 direct_cluster_grid_path_clear_batch.  min_d2 <= 1 needs no field, and a stale or missing one is not looked
+ *                 at.  Penalties play no part, because they are finite.
+ *   Label         label[v], int32, in the map's layout (x * max_y * max_z + y * max_z + z): -1 for a voxel that is not enterable,
+ *                 otherwise the SMALLEST linear index among the voxels of v's component in the graph "enterable voxels, 26
+ *                 neighbours inside the map".  A pure function of map bytes, stored field and min_d2: bit for bit the same
+ *                 whatever the launch shape and however often it is rebuilt.
+ *   Size          size[v], int32: the number of voxels of v's component for an enterable v, else 0.
+ *   Stats         stats[4] (int64, HOST, may be NULL): enterable voxels, number of components, size of the largest component, its
+ *                 label (-1 without one; ties go to the smaller label).
+ *   Reachability  of a pair (s, g), with the codes of the path calls (DIRECT_GRID_PATH_*):
+ *                   BAD_ENDPOINT  if s or g lies outside the map;
+ *                   OK            if s == g, whatever the voxel's byte;
+ *                   NO_PATH       if g is not enterable;
+ *                   if s is enterable: OK iff label[s] == label[g];
+ *                   if s is NOT enterable: OK iff some 26-neighbour n of s inside the map is enterable and has
+ *                                 label[n] == label[g] (the path calls never look at the start's byte, D2 or penalty);
+ *                   NO_PATH       otherwise.
+ *                 This is exactly the rtn of the pairwise and fan calls with OVERFLOW folded into OK.  ROUND_LIMIT cannot be
+ *                 foretold: a query that would run out of max_rounds is judged as if it had not.
+ * direct_cluster_free_components builds labels and sizes for the map the handle holds NOW, into one resident pair of int32
+ * buffers per handle (4 B per voxel each, allocated by the first build, never shrunk, freed in direct_cluster_destroy).  It runs
+ * on the handle's stream and synchronises before it returns; direct_cluster_last_ms covers its kernels.  DIRECT_ERR_INVALID,
+ * nothing launched: a NULL handle or no map; min_d2 < 0; min_d2 > 1 without a VALID distance field, or with min_d2 above the
+ * cap2 the field was built with (the refusals of the clear path call, with the same wording).  Method: a union-find by smaller
+ * index, per 8^3 tile in LDS, then across tile borders in global memory, then a flatten; all integer, every loop bounded - a
+ * bound that is passed is DIRECT_ERR_DEVICE, never a hang.
+ * direct_cluster_get_free_components fetches label and size ([max_x*max_y*max_z] int32 each) into memory kind `mem` and the
+ * normal form of the floor the set was built with (<= 1 -> 0) into *min_d2_built (HOST); any of the three may be NULL.
+ * direct_cluster_reachable_batch judges n pairs: n > 0 and NOT limited by max_batch; starts[n][3] and goals[n][3] in memory
+ * kind mem_in (a device-resident goal list passes through); outputs in memory kind `mem`, any may be NULL: rtn[n],
+ * goal_label[n], goal_size[n] - goal_label is -1 and goal_size is 0 where the goal is outside the map or not enterable.  It
+ * does no relaxation: one lane per pair, up to 26 label loads for a start that is not enterable.  DIRECT_ERR_INVALID, nothing
+ * launched: a NULL handle, struct, starts or goals; n <= 0; a bad mem / mem_in; min_d2 < 0; no VALID labels; an in->min_d2 whose
+ * normal form differs from the one the labels were built with - a label set never gets two meanings.  Host arrays go through
+ * staging blocks of the call's own, grown on demand and freed in direct_cluster_destroy.
+ * STALENESS.  Labels are marked stale by direct_cluster_set_map and direct_cluster_map_from_cloud, whether or not they succeed;
+ * labels built with min_d2 > 1 also by every direct_cluster_distance_field call.  A stale set is refused by the fetch and by
+ * direct_cluster_reachable_batch, never rebuilt silently.  The build leaves the map, the field, resident clusters, the floor
+ * tables and every path workspace alone. */
+direct_status_t direct_cluster_free_components(direct_cluster_handle_t h, int32_t min_d2, int64_t* stats /* HOST [4] or NULL */);
+direct_status_t direct_cluster_get_free_components(direct_cluster_handle_t h, int32_t mem, int32_t* label, int32_t* size,
+                                                   int32_t* min_d2_built /* HOST or NULL */);
+typedef struct {
+  int64_t n;                 /* pairs, > 0; not limited by max_batch */
+  int32_t mem_in;            /* direct_mem_t of starts and goals */
+  int32_t min_d2;            /* >= 0; its normal form must be the one the labels were built with */
+  const int32_t* starts;     /* [n][3] */
+  const int32_t* goals;      /* [n][3] */
+} direct_reachable_in_t;
+
+typedef struct {
+  int32_t mem;               /* direct_mem_t: where every array below lives */
+  int32_t reserved;
+  int32_t* rtn;              /* [n] or NULL, DIRECT_GRID_PATH_OK / _NO_PATH / _BAD_ENDPOINT */
+  int32_t* goal_label;       /* [n] or NULL */
+  int32_t* goal_size;        /* [n] or NULL */
+} direct_reachable_out_t;
+
+direct_status_t direct_cluster_reachable_batch(direct_cluster_handle_t h, const direct_reachable_in_t* in,
+                                               direct_reachable_out_t* out);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
  * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch /
- * grid_path_clear_batch / grid_path_fan_batch call (the fan: its init, bounds, rounds, read-back and stats kernels with the
- * read-backs of the round counters between them, not the copies of host arrays) */
+ * grid_path_clear_batch / grid_path_fan_batch / free_components / reachable_batch call (the fan: its init, bounds, rounds,
+ * read-back and stats kernels with the read-backs of the round counters between them, not the copies of host arrays; the
+ * components: the two clears and the four kernels of a build, the one kernel of reachable_batch) */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
