@@ -194,6 +194,24 @@ class ReachableOut(C.Structure):  # direct_reachable_out_t (include/direct_clust
 REACHABLE_OUTPUTS = ("rtn", "goal_label", "goal_size")   # the arrays of ReachableOut
 
 
+class ClusterCorridorIn(C.Structure):  # direct_cluster_corridor_in_t (include/direct_cluster.h)
+    _fields_ = [("batch", C.c_int32), ("path_capacity", C.c_int32), ("mem_in", C.c_int32), ("itr_inflate_max", C.c_int32),
+                ("path_xyz", C.c_void_p), ("path_len", C.c_void_p), ("itr_cluster_max", C.c_int32), ("pop_back", C.c_int32),
+                ("seg_capacity", C.c_int32), ("p_max", C.c_int32), ("plane_dtype", C.c_int32), ("reserved", C.c_int32),
+                ("resolution", C.c_double), ("map_lower", C.c_double * 3)]
+
+
+class ClusterCorridorOut(C.Structure):  # direct_cluster_corridor_out_t (include/direct_cluster.h)
+    _fields_ = [("mem", C.c_int32), ("reserved", C.c_int32), ("n_seg", C.c_void_p), ("n_planes", C.c_void_p), ("planes", C.c_void_p),
+                ("seeds", C.c_void_p), ("centers", C.c_void_p), ("rtn", C.c_void_p)]
+
+
+CLUSTER_CORRIDOR_OUTPUTS = ("n_seg", "n_planes", "planes", "seeds", "centers", "rtn")   # the arrays of ClusterCorridorOut
+# direct_cluster_corridor_batch(handle, ClusterCorridorIn*, ClusterCorridorOut*, int64 stats[4] or NULL)
+CLUSTER_CORRIDOR_ARGTYPES = (C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+CLUSTER_CORRIDOR_STATS = ("rounds", "due_seeds", "unique_seeds", "pops")   # stats[4]
+
+
 class LaunchInfo(C.Structure):  # direct_ddp_launch_info_t
     _fields_ = [
         ("dynamic", C.c_int32), ("shared_search", C.c_int32), ("pair_trials", C.c_int32), ("single_steps", C.c_int32),

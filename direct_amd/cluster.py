@@ -37,6 +37,7 @@ CubeCorridorIn, CubeCorridorOut = abi.CubeCorridorIn, abi.CubeCorridorOut  # dir
 GridPathClearIn, GridPathClearOut = abi.GridPathClearIn, abi.GridPathClearOut  # direct_grid_path_clear_in_t, direct_grid_path_clear_out_t
 GridPathFanIn, GridPathFanOut = abi.GridPathFanIn, abi.GridPathFanOut  # direct_grid_path_fan_in_t, direct_grid_path_fan_out_t
 ReachableIn, ReachableOut = abi.ReachableIn, abi.ReachableOut  # direct_reachable_in_t, direct_reachable_out_t
+ClusterCorridorIn, ClusterCorridorOut = abi.ClusterCorridorIn, abi.ClusterCorridorOut  # direct_cluster_corridor_in_t, direct_cluster_corridor_out_t
 
 
 EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_last_error", "direct_cluster_set_map",
@@ -46,7 +47,7 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
            "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch",
            "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
-           "direct_cluster_reachable_batch")
+           "direct_cluster_reachable_batch", "direct_cluster_corridor_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -55,6 +56,8 @@ MAP_REPLACE, MAP_ADD = 0, 1
 PLAN_CHECK_INVALID = -1
 DIST_NONE = 0x7fffffff
 CUBE_CORRIDOR_OK, CUBE_CORRIDOR_OVERFLOW, CUBE_CORRIDOR_BAD_PATH = 0, 1, 2
+CLUSTER_CORRIDOR_OK, CLUSTER_CORRIDOR_OVERFLOW, CLUSTER_CORRIDOR_BAD_PATH = 0, 1, 2
+CLUSTER_CORRIDOR_NO_POLYTOPE, CLUSTER_CORRIDOR_TOO_MANY_PLANES = 3, 4
 _BOUND = False
 
 
@@ -89,6 +92,7 @@ def _lib():
         L.direct_cluster_free_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_get_free_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_reachable_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_corridor_batch.argtypes = list(abi.CLUSTER_CORRIDOR_ARGTYPES)
         _BOUND = True
     return L
 
@@ -451,13 +455,32 @@ class ClusterGenerator:
         out["info"] = info
         return out
 
-    def _cube_corridors(self, call, paths, path_len, map_lower, resolution, itr_inflate_max, pop_back, seg_capacity, p_max, dtype):
-        """the two cube corridor calls: call(handle, address of the input struct, address of the output struct) -> status"""
+    def cluster_corridors(self, paths, path_len, map_lower, resolution, itr_inflate_max=1000, itr_cluster_max=50, pop_back=True,
+                          seg_capacity=64, p_max=64, dtype=np.float64):
+        """The corridors of a batch of grid paths in the mode the reference ships, is_cluster_on == true: every polytope the hull of
+        the voxel cluster grown from its seed (direct_cluster_corridor_batch).  The walk runs on the device; per round the due seeds
+        are de-duplicated by voxel and generated in chunks of max_batch; per row the result is, bit for bit, the lock-step walk over
+        polygon_generation + hull_planes.  Arguments, kinds (NumPy arrays or device tensors) and layouts as cube_corridors;
+        itr_cluster_max=0 gives cubes.  The call invalidates resident clusters.
+        -> dict(n_seg [B], n_planes [B][S], planes [B][S][p_max][4], seeds [B][S][3], centers [B][S][3], rtn [B] (CLUSTER_CORRIDOR_*),
+        stats: dict(rounds, due_seeds, unique_seeds, pops)); entries from a row's n_seg on are zero"""
+        stats = np.zeros(4, np.int64)
+        par = ClusterCorridorIn(itr_cluster_max=int(itr_cluster_max))
+        fn = _lib().direct_cluster_corridor_batch
+        out = self._cube_corridors(lambda h, p, o: fn(h, p, o, stats.ctypes.data), paths, path_len, map_lower, resolution, itr_inflate_max,
+                                   pop_back, seg_capacity, p_max, dtype, par=par, out_type=ClusterCorridorOut, keys=abi.CLUSTER_CORRIDOR_OUTPUTS)
+        out["stats"] = {k: int(v) for k, v in zip(abi.CLUSTER_CORRIDOR_STATS, stats)}
+        return out
+
+    def _cube_corridors(self, call, paths, path_len, map_lower, resolution, itr_inflate_max, pop_back, seg_capacity, p_max, dtype,
+                        par=None, out_type=CubeCorridorOut, keys=abi.CUBE_CORRIDOR_OUTPUTS):
+        """the corridor calls: call(handle, address of the input struct, address of the output struct) -> status.  par: an input
+        struct with the call's own fields set (None: CubeCorridorIn); out_type / keys: its output struct and that struct's arrays"""
         lower = np.asarray(map_lower, np.float64).reshape(3)
         f32 = np.dtype(dtype) == np.float32
-        par = CubeCorridorIn(itr_inflate_max=int(itr_inflate_max), pop_back=int(bool(pop_back)), seg_capacity=int(seg_capacity),
-                             p_max=int(p_max), plane_dtype=abi.F32 if f32 else abi.F64, resolution=float(resolution),
-                             map_lower=(C.c_double * 3)(*lower))
+        par = CubeCorridorIn() if par is None else par
+        par.itr_inflate_max, par.pop_back, par.seg_capacity, par.p_max = int(itr_inflate_max), int(bool(pop_back)), int(seg_capacity), int(p_max)
+        par.plane_dtype, par.resolution, par.map_lower = abi.F32 if f32 else abi.F64, float(resolution), (C.c_double * 3)(*lower)
         S, P = int(seg_capacity), int(p_max)
         if isinstance(paths, np.ndarray) or not hasattr(paths, "data_ptr"):
             paths, path_len = np.ascontiguousarray(paths, np.int32), np.ascontiguousarray(path_len, np.int32)
@@ -481,7 +504,8 @@ class ClusterGenerator:
         par.path_xyz, par.path_len = ptr(paths), ptr(path_len)
         out = dict(n_seg=z(B, np.int32), n_planes=z((B, S), np.int32), planes=z((B, S, P, 4), real), seeds=z((B, S, 3), real),
                    centers=z((B, S, 3), real), cube_idx=z((B, S, 6), np.int32), rtn=z(B, np.int32))
-        o = CubeCorridorOut(mem, 0, *[ptr(out[k]) for k in abi.CUBE_CORRIDOR_OUTPUTS])
+        out = {k: out[k] for k in keys}
+        o = out_type(mem, 0, *[ptr(out[k]) for k in keys])
         _check(call(self.h, C.addressof(par), C.addressof(o)))
         return out
 

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/direct_cluster.h"
+#include "cluster_corridor_math.h"
 #include "cube_corridor_clear_math.h"
 #include "cube_corridor_math.h"
 #include "free_comp_math.h"
@@ -993,6 +994,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "cube_corridor.h"
 #include "cube_corridor_clear.h"
 #include "free_comp.h"
+#include "cluster_corridor.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1052,6 +1054,8 @@ struct direct_cluster_handle_s {
   fc::Key comp_key = {};                   // what the resident labels were built from (valid == 0: none)
   unsigned long long map_gen = 0, field_gen = 0;  // calls that set the map / built a field so far: the labels' staleness key
   hs::Block reach_in, reach_out;  // device staging of reachable_batch's host inputs / host outputs, grown on demand
+  hs::Block corr_ws;   // workspace of corridor_batch (walk states, plane stacks, owner table, seed list, a chunk's hull outputs), grown on demand
+  hs::Block corr_in, corr_out;  // device staging of its host inputs / host outputs, grown on demand
 };
 
 namespace {
@@ -1213,10 +1217,11 @@ hipError_t download_fields(direct_cluster_handle_t h, double* dist, size_t n, in
                         mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
 }
 
-// cube_corridor_batch and cube_corridor_clear_batch.  What both refuse, in the plain call's order; DIRECT_OK: nothing to refuse.
+// cube_corridor_batch, cube_corridor_clear_batch and corridor_batch, whose structs share these field names.  What all refuse, in
+// the plain call's order; DIRECT_OK: nothing to refuse.
 // `more` is a further refusal that the call's arguments alone decide (or null): it comes before what the handle holds.
-direct_status_t cube_corridor_refusal(direct_cluster_handle_t h, const direct_cube_corridor_in_t* in, const direct_cube_corridor_out_t* out,
-                                      const char* more) {
+template <class In, class Out>
+direct_status_t cube_corridor_refusal(direct_cluster_handle_t h, const In* in, const Out* out, const char* more) {
   if (!h || !in || !out || !in->path_xyz || !in->path_len) return cfail(DIRECT_ERR_INVALID, "null argument");
   if (in->batch <= 0 || in->path_capacity <= 0 || in->seg_capacity <= 0 || in->itr_inflate_max <= 0)
     return cfail(DIRECT_ERR_INVALID, "batch, path_capacity, seg_capacity and itr_inflate_max must be positive");
@@ -1277,6 +1282,101 @@ direct_status_t cube_corridor_run(direct_cluster_handle_t h, const direct_cube_c
   if (e == hipSuccess) e = after();
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string(who) + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+// The device part of polygon_generation_batch for `batch` <= max_batch seeds in DEVICE memory (seeds[batch][3]): flagClear, the
+// cube, the rounds of polytopeCluster_cpu and the emit into DEVICE outputs (any may be null).  Enqueues on the handle's stream and
+// waits for its own liveness read-backs, the last of which leaves the elements' counters in `el`; events, the copies of host arrays
+// and resident_batch are the caller's.
+direct_status_t generation_run(direct_cluster_handle_t h, int batch, const int* seeds, int itr_inflate_max, int itr_cluster_max, int32_t* dv,
+                               int32_t* dc, int32_t* dn, int32_t* di, int32_t* dr, std::vector<Elem>& el) {
+  Dev& D = h->D;
+  const int gblocks = std::min((D.G + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_flags_init, dim3(gblocks, batch), dim3(256), 0, h->stream, D, (const uint8_t*)nullptr);  // flagClear CS:20-26
+  hipLaunchKernelGGL(k_inflate, dim3(batch), dim3(256), 0, h->stream, D, seeds, itr_inflate_max);
+  CHIP_TRY(hipGetLastError());
+  el.resize(batch);
+  auto fetch = [&]() -> hipError_t {
+    hipError_t e = hipMemcpyAsync(el.data(), D.el, (size_t)batch * sizeof(Elem), hipMemcpyDeviceToHost, h->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+  };
+  CHIP_TRY(fetch());
+  // polytopeCluster_cpu (CS:295-392).  No launch of a round depends on a count the round produces (grid-stride or
+  // capacity-sized kernels over device-resident counters; workgroups of finished seeds return at once), so the host enqueues rounds
+  // blindly, kRoundsPerCheck at a time, and only then looks whether any seed is still growing: one read-back per
+  // kRoundsPerCheck rounds instead of three per round (the reference's CUDA twin, cluster_server.cu:628-685, copies
+  // per round as well).
+  constexpr int kRoundsPerCheck = 4;
+  for (int round = 0; round < itr_cluster_max;) {
+    int live = 0;
+    for (const Elem& E : el) live += E.live ? 1 : 0;
+    if (!live) break;
+    const int n = std::min(kRoundsPerCheck, itr_cluster_max - round);
+    for (int r = 0; r < n; r++) {
+      hipLaunchKernelGGL(k_mark, dim3(128, batch), dim3(256), 0, h->stream, D);
+      hipLaunchKernelGGL(k_compact_count, dim3(kCompactBlocks, batch), dim3(256), 0, h->stream, D);
+      hipLaunchKernelGGL(k_compact_write, dim3(kCompactBlocks, batch), dim3(256), 0, h->stream, D);
+      // one workgroup per candidate SLOT: the slots beyond a seed's candidate count return at once (640 k empty
+      // workgroups cost ~0.1 ms; a persistent ticket kernel with the rays' voxels staged in LDS was built and measured
+      // 1.6 - 2 x slower: thousands of short workgroups balance the seeds' very different loads better, and the flag
+      // bytes of a round's rays live in L2 anyway)
+      hipLaunchKernelGGL(k_chunk_box, dim3(D.nchunk, batch), dim3(256), 0, h->stream, D);
+      hipLaunchKernelGGL(k_convex<false>, dim3(std::min(D.kcap, h->convex_grid), batch), dim3(256), 0, h->stream, D);
+      if (D.kwords <= 256) {
+        hipLaunchKernelGGL(k_resolve_fast, dim3(batch), dim3(64), 0, h->stream, D);
+        hipLaunchKernelGGL(k_apply, dim3((D.kcap + 255) / 256, batch), dim3(256), 0, h->stream, D);
+      }
+      else hipLaunchKernelGGL(k_resolve_pipe, dim3(batch), dim3(64), (size_t)D.kwords * 8, h->stream, D);
+    }
+    CHIP_TRY(hipGetLastError());
+    round += n;
+    CHIP_TRY(fetch());
+  }
+  hipLaunchKernelGGL(k_emit, dim3(64, batch), dim3(256), 0, h->stream, D, batch, dv, dc, dn, di, dr);
+  return DIRECT_OK;
+}
+
+// The scratch of the hull kernels, allocated by the first call that needs it: all or nothing, so that a retry starts clean
+direct_status_t hull_workspace(direct_cluster_handle_t h) {
+  if (h->have_hull) return DIRECT_OK;
+  const Dev& D = h->D;
+  HullDev& H = h->H;
+  const size_t B = h->cfg.max_batch;
+  H.QX = 2 * D.max_x + 1; H.QY = 2 * D.max_y + 1; H.QZ = 2 * D.max_z + 1;
+  H.half_words = (size_t)H.QY * H.QZ + (size_t)H.QX * H.QZ + (size_t)H.QX * H.QY;
+  H.line_words = 2 * H.half_words;
+  const hipError_t ae = hs::alloc_all(h->allocs, {
+      hs::want(&H.he, B * sizeof(HullElem)), hs::want(&H.lines, B * H.line_words * sizeof(int)),
+      hs::want(&H.cand, B * 3 * hull::kCandCap * sizeof(int)), hs::want(&H.first, B * hull::kCandCap * sizeof(int)),
+      hs::want(&H.isv, B * hull::kCandCap * sizeof(int)), hs::want(&H.raw, B * hull::kRawCap * 4 * sizeof(hull::i64)),
+      hs::want(&H.sorted, B * hull::kRawCap * 4 * sizeof(hull::i64)), hs::want(&H.vq, B * hull::kCandCap * 3 * sizeof(int))});
+  if (ae != hipSuccess) {
+    H = HullDev{};
+    return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: scratch allocation: ") + hipGetErrorString(ae));
+  }
+  h->have_hull = true;
+  return DIRECT_OK;
+}
+
+// The device part of hull_planes_batch for `batch` <= max_batch clusters: sx / sn are DEVICE voxels and counts that replace the
+// resident clusters, or null for the resident ones; dev[8] are DEVICE outputs in the public call's order (planes, plane_int,
+// n_planes, vertices, n_vertices, center, degenerate, rtn), any may be null.  Enqueues only.
+direct_status_t hull_run(direct_cluster_handle_t h, int batch, const int32_t* sx, const int32_t* sn, double resolution, const double* map_lower,
+                         int plane_capacity, int vertex_capacity, void* const* dev) {
+  Dev& D = h->D;
+  HullDev& H = h->H;
+  const size_t nb = (size_t)batch;
+  CHIP_TRY(hipMemset2DAsync(H.lines, H.line_words * sizeof(int), 0x7f, H.half_words * sizeof(int), nb, h->stream));
+  CHIP_TRY(hipMemset2DAsync(H.lines + H.half_words, H.line_words * sizeof(int), 0x80, H.half_words * sizeof(int), nb, h->stream));
+  CHIP_TRY(hipMemsetAsync(H.he, 0, nb * sizeof(HullElem), h->stream));
+  hipLaunchKernelGGL(k_hull_src, dim3(32, batch), dim3(256), 0, h->stream, D, H, batch, sx, sn);
+  hipLaunchKernelGGL(k_hull_lines, dim3(batch), dim3(256), 0, h->stream, D, H);
+  hipLaunchKernelGGL(k_hull_cand, dim3(batch), dim3(256), 0, h->stream, D, H);
+  hipLaunchKernelGGL(k_hull_edges, dim3(64, batch), dim3(256), 0, h->stream, H);
+  hipLaunchKernelGGL(k_hull_finish, dim3(batch), dim3(256), 0, h->stream, H, resolution, map_lower[0], map_lower[1], map_lower[2],
+                     plane_capacity, vertex_capacity, (double*)dev[0], (long long*)dev[1], (int32_t*)dev[2], (double*)dev[3],
+                     (int32_t*)dev[4], (double*)dev[5], (int32_t*)dev[6], (int32_t*)dev[7]);
   return DIRECT_OK;
 }
 }  // namespace
@@ -1352,7 +1452,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
-                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out})
+                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out})
     hs::release(*b);
   hs::destroy(h->ev);
   delete h;
@@ -1459,53 +1559,13 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
   h->resident_batch = 0;
   CHIP_TRY(hipMemcpyAsync(h->seeds, seeds, (size_t)batch * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hs::start(h->ev, h->stream));
-  const int gblocks = std::min((D.G + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_flags_init, dim3(gblocks, batch), dim3(256), 0, h->stream, D, (const uint8_t*)nullptr);  // flagClear CS:20-26
-  hipLaunchKernelGGL(k_inflate, dim3(batch), dim3(256), 0, h->stream, D, (const int*)h->seeds, itr_inflate_max);
-  CHIP_TRY(hipGetLastError());
-  std::vector<Elem> el(batch);
-  auto fetch = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(el.data(), D.el, (size_t)batch * sizeof(Elem), hipMemcpyDeviceToHost, h->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
-  };
-  CHIP_TRY(fetch());
-  // polytopeCluster_cpu (CS:295-392).  No launch of a round depends on a count the round produces (grid-stride or
-  // capacity-sized kernels over device-resident counters; workgroups of finished seeds return at once), so the host enqueues rounds
-  // blindly, kRoundsPerCheck at a time, and only then looks whether any seed is still growing: one read-back per
-  // kRoundsPerCheck rounds instead of three per round (the reference's CUDA twin, cluster_server.cu:628-685, copies
-  // per round as well).
-  constexpr int kRoundsPerCheck = 4;
-  for (int round = 0; round < itr_cluster_max;) {
-    int live = 0;
-    for (const Elem& E : el) live += E.live ? 1 : 0;
-    if (!live) break;
-    const int n = std::min(kRoundsPerCheck, itr_cluster_max - round);
-    for (int r = 0; r < n; r++) {
-      hipLaunchKernelGGL(k_mark, dim3(128, batch), dim3(256), 0, h->stream, D);
-      hipLaunchKernelGGL(k_compact_count, dim3(kCompactBlocks, batch), dim3(256), 0, h->stream, D);
-      hipLaunchKernelGGL(k_compact_write, dim3(kCompactBlocks, batch), dim3(256), 0, h->stream, D);
-      // one workgroup per candidate SLOT: the slots beyond a seed's candidate count return at once (640 k empty
-      // workgroups cost ~0.1 ms; a persistent ticket kernel with the rays' voxels staged in LDS was built and measured
-      // 1.6 - 2 x slower: thousands of short workgroups balance the seeds' very different loads better, and the flag
-      // bytes of a round's rays live in L2 anyway)
-      hipLaunchKernelGGL(k_chunk_box, dim3(D.nchunk, batch), dim3(256), 0, h->stream, D);
-      hipLaunchKernelGGL(k_convex<false>, dim3(std::min(D.kcap, h->convex_grid), batch), dim3(256), 0, h->stream, D);
-      if (D.kwords <= 256) {
-        hipLaunchKernelGGL(k_resolve_fast, dim3(batch), dim3(64), 0, h->stream, D);
-        hipLaunchKernelGGL(k_apply, dim3((D.kcap + 255) / 256, batch), dim3(256), 0, h->stream, D);
-      }
-      else hipLaunchKernelGGL(k_resolve_pipe, dim3(batch), dim3(64), (size_t)D.kwords * 8, h->stream, D);
-    }
-    CHIP_TRY(hipGetLastError());
-    round += n;
-    CHIP_TRY(fetch());
-  }
   int32_t *dv = vertex_idx, *dc = cluster_xyz, *dn = cluster_num, *di = cluster_iters, *dr = rtn;
   if (mem == DIRECT_MEM_HOST) {  // host outputs are staged in buffers the handle owns (allocated once, in create)
     dv = vertex_idx ? h->st_vertex : nullptr; dc = cluster_xyz ? h->st_xyz : nullptr; dn = cluster_num ? h->st_num : nullptr;
     di = cluster_iters ? h->st_iters : nullptr; dr = rtn ? h->st_rtn : nullptr;
   }
-  hipLaunchKernelGGL(k_emit, dim3(64, batch), dim3(256), 0, h->stream, D, batch, dv, dc, dn, di, dr);
+  std::vector<Elem> el;
+  if (const direct_status_t rc = generation_run(h, batch, h->seeds, itr_inflate_max, itr_cluster_max, dv, dc, dn, di, dr, el)) return rc;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   if (e == hipSuccess && mem == DIRECT_MEM_HOST) {
@@ -1593,24 +1653,7 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
   if (cluster_xyz) h->resident_batch = 0;  // the voxels are packed into the handle's cluster storage: the generation's clusters are gone
   CHIP_TRY(hipSetDevice(h->cfg.device));
   Dev& D = h->D;
-  HullDev& H = h->H;
-  const size_t B = h->cfg.max_batch;
-  if (!h->have_hull) {
-    H.QX = 2 * D.max_x + 1; H.QY = 2 * D.max_y + 1; H.QZ = 2 * D.max_z + 1;
-    H.half_words = (size_t)H.QY * H.QZ + (size_t)H.QX * H.QZ + (size_t)H.QX * H.QY;
-    H.line_words = 2 * H.half_words;
-    // all or nothing: a failed allocation frees what this call has allocated, so that a retry starts clean
-    const hipError_t ae = hs::alloc_all(h->allocs, {
-        hs::want(&H.he, B * sizeof(HullElem)), hs::want(&H.lines, B * H.line_words * sizeof(int)),
-        hs::want(&H.cand, B * 3 * hull::kCandCap * sizeof(int)), hs::want(&H.first, B * hull::kCandCap * sizeof(int)),
-        hs::want(&H.isv, B * hull::kCandCap * sizeof(int)), hs::want(&H.raw, B * hull::kRawCap * 4 * sizeof(hull::i64)),
-        hs::want(&H.sorted, B * hull::kRawCap * 4 * sizeof(hull::i64)), hs::want(&H.vq, B * hull::kCandCap * 3 * sizeof(int))});
-    if (ae != hipSuccess) {
-      H = HullDev{};
-      return cfail(DIRECT_ERR_DEVICE, std::string("hull_planes_batch: scratch allocation: ") + hipGetErrorString(ae));
-    }
-    h->have_hull = true;
-  }
+  if (const direct_status_t rc = hull_workspace(h)) return rc;
   // device views of the outputs: the caller's pointers, or slices of one staging block for host outputs (nothing is filled:
   // the host arrays hold what the block held wherever k_hull_finish does not write)
   const size_t nb = (size_t)batch;
@@ -1635,16 +1678,7 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
     sx = h->st_xyz; sn = h->st_num;
   }
   CHIP_TRY(hs::start(h->ev, h->stream));
-  CHIP_TRY(hipMemset2DAsync(H.lines, H.line_words * sizeof(int), 0x7f, H.half_words * sizeof(int), nb, h->stream));
-  CHIP_TRY(hipMemset2DAsync(H.lines + H.half_words, H.line_words * sizeof(int), 0x80, H.half_words * sizeof(int), nb, h->stream));
-  CHIP_TRY(hipMemsetAsync(H.he, 0, nb * sizeof(HullElem), h->stream));
-  hipLaunchKernelGGL(k_hull_src, dim3(32, batch), dim3(256), 0, h->stream, D, H, batch, sx, sn);
-  hipLaunchKernelGGL(k_hull_lines, dim3(batch), dim3(256), 0, h->stream, D, H);
-  hipLaunchKernelGGL(k_hull_cand, dim3(batch), dim3(256), 0, h->stream, D, H);
-  hipLaunchKernelGGL(k_hull_edges, dim3(64, batch), dim3(256), 0, h->stream, H);
-  hipLaunchKernelGGL(k_hull_finish, dim3(batch), dim3(256), 0, h->stream, H, resolution, map_lower[0], map_lower[1], map_lower[2],
-                     plane_capacity, vertex_capacity, (double*)dev[0], (long long*)dev[1], (int32_t*)dev[2], (double*)dev[3],
-                     (int32_t*)dev[4], (double*)dev[5], (int32_t*)dev[6], (int32_t*)dev[7]);
+  if (const direct_status_t rc = hull_run(h, batch, sx, sn, resolution, map_lower, plane_capacity, vertex_capacity, dev)) return rc;
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   e = hs::drain(h->stream, hs::stage_download(st, h->stream, e));
@@ -1848,6 +1882,92 @@ direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t
     s.used = ++h->floor_clock;
   }
   if (info) { info[0] = hit ? 0 : 1; info[1] = neutral ? count : h->floor_slot[slot].count; }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_corridor_batch(direct_cluster_handle_t h, const direct_cluster_corridor_in_t* in, direct_cluster_corridor_out_t* out,
+                                              int64_t* stats) {
+  if (const direct_status_t rc = cube_corridor_refusal(h, in, out, in && in->itr_cluster_max < 0 ? "itr_cluster_max must not be negative" : nullptr))
+    return rc;
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  h->resident_batch = 0;  // the chunks' generations run in the handle's cluster storage: the last generation's clusters are gone
+  if (const direct_status_t rc = hull_workspace(h)) return rc;
+  const Dev& D = h->D;
+  const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
+  const size_t P = (size_t)in->p_max, MB = (size_t)h->cfg.max_batch;
+  const size_t r = in->plane_dtype == DIRECT_F32 ? sizeof(float) : sizeof(double);
+  CorrDev A = {};
+  A.batch = in->batch; A.path_cap = in->path_capacity; A.seg_cap = in->seg_capacity; A.p_max = in->p_max; A.pop_back = in->pop_back ? 1 : 0;
+  A.X = D.max_x; A.Y = D.max_y; A.Z = D.max_z;
+  A.res = in->resolution;
+  for (int a = 0; a < 3; a++) A.lower[a] = in->map_lower[a];
+  hs::Stage ws(false), si(in->mem_in == DIRECT_MEM_HOST), so(out->mem == DIRECT_MEM_HOST);
+  hs::stage_scratch(ws, &A.rows, B * sizeof(kc::Row));
+  hs::stage_scratch(ws, &A.st_planes, segs * P * 4 * sizeof(double));
+  hs::stage_scratch(ws, &A.st_np, segs * sizeof(int32_t));
+  hs::stage_scratch(ws, &A.st_seeds, segs * 3 * sizeof(double));
+  hs::stage_scratch(ws, &A.st_centers, segs * 3 * sizeof(double));
+  hs::stage_scratch(ws, &A.table, (size_t)D.G * sizeof(int));
+  hs::stage_scratch(ws, &A.seed_list, B * 3 * sizeof(int32_t));
+  hs::stage_scratch(ws, &A.cnt, 4 * sizeof(unsigned long long));
+  hs::stage_scratch(ws, &A.h_planes, MB * P * 4 * sizeof(double));
+  hs::stage_scratch(ws, &A.h_np, MB * sizeof(int32_t));
+  hs::stage_scratch(ws, &A.h_center, MB * 3 * sizeof(double));
+  hs::stage_scratch(ws, &A.h_rtn, MB * sizeof(int32_t));
+  hs::stage_in(si, &A.path_xyz, in->path_xyz, slots * 3 * sizeof(int32_t));
+  hs::stage_in(si, &A.path_len, in->path_len, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_seg, out->n_seg, B * sizeof(int32_t));
+  hs::stage_out(so, &A.n_planes, out->n_planes, segs * sizeof(int32_t));
+  hs::stage_out(so, &A.planes, out->planes, segs * P * 4 * r);
+  hs::stage_out(so, &A.seeds, out->seeds, segs * 3 * r);
+  hs::stage_out(so, &A.centers, out->centers, segs * 3 * r);
+  hs::stage_out(so, &A.rtn, out->rtn, B * sizeof(int32_t));
+  CHIP_TRY(hs::stage_upload(ws, h->corr_ws, h->stream));
+  CHIP_TRY(hs::stage_upload(si, h->corr_in, h->stream));
+  CHIP_TRY(hs::stage_upload(so, h->corr_out, h->stream));
+  // the owner table starts every call untouched (a call that failed half way may have left entries behind); rounds reset what they touch
+  CHIP_TRY(hipMemsetAsync(A.table, 0x7f, (size_t)D.G * sizeof(int), h->stream));
+  CHIP_TRY(hipMemsetAsync(A.cnt, 0, 4 * sizeof(unsigned long long), h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  void* const hull_out[8] = {A.h_planes, nullptr, A.h_np, nullptr, nullptr, A.h_center, nullptr, A.h_rtn};
+  unsigned long long cnt[4] = {0, 0, 0, 0};
+  std::vector<Elem> el;
+  long long rounds = 0;
+  bool ended = false;
+  // Every unfinished row either ends or consumes a point per round, and a row has at most path_capacity points: round
+  // path_capacity (counted from 0) finds nothing due.  A loop that gets past it reports DIRECT_ERR_DEVICE.
+  for (int round = 0; round <= in->path_capacity && !ended; round++) {
+    hipLaunchKernelGGL(k_corr_advance, dim3(in->batch), dim3(64), 0, h->stream, A, round == 0 ? 1 : 0);
+    hipLaunchKernelGGL(k_corr_unique, dim3(1), dim3(1024), 0, h->stream, A);
+    CHIP_TRY(hipGetLastError());
+    CHIP_TRY(hipMemcpyAsync(cnt, A.cnt, sizeof cnt, hipMemcpyDeviceToHost, h->stream));  // the round's one small word
+    CHIP_TRY(hipStreamSynchronize(h->stream));
+    if (cnt[0] == 0) {
+      ended = true;
+      break;
+    }
+    rounds++;
+    for (size_t lo = 0; lo < cnt[0]; lo += MB) {
+      const int nb = (int)std::min<size_t>(MB, cnt[0] - lo);
+      if (const direct_status_t rc = generation_run(h, nb, A.seed_list + 3 * lo, in->itr_inflate_max, in->itr_cluster_max, nullptr, nullptr,
+                                                    nullptr, nullptr, nullptr, el))
+        return rc;
+      if (const direct_status_t rc = hull_run(h, nb, nullptr, nullptr, in->resolution, in->map_lower, in->p_max, 1, hull_out)) return rc;
+      hipLaunchKernelGGL(k_corr_append, dim3(in->batch), dim3(64), 0, h->stream, D, A, (int)lo, nb);
+      CHIP_TRY(hipGetLastError());
+    }
+  }
+  if (!ended) {
+    (void)hipStreamSynchronize(h->stream);
+    return cfail(DIRECT_ERR_DEVICE, "corridor_batch: rows still walking after path_capacity + 1 rounds");
+  }
+  if (in->plane_dtype == DIRECT_F32) hipLaunchKernelGGL(k_corr_emit<float>, dim3(in->batch), dim3(256), 0, h->stream, A);
+  else hipLaunchKernelGGL(k_corr_emit<double>, dim3(in->batch), dim3(256), 0, h->stream, A);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("corridor_batch: ") + hipGetErrorString(e));
+  if (stats) { stats[0] = rounds; stats[1] = (int64_t)cnt[1]; stats[2] = (int64_t)cnt[2]; stats[3] = (int64_t)cnt[3]; }
   return DIRECT_OK;
 }
 

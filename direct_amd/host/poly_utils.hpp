@@ -19,6 +19,9 @@
 //     cube of its seed voxel) for many paths in ONE device call, direct_cluster_cube_corridor_batch: no rounds at all
 //   * cubeCorridorClearBatch(gridPaths, corridors, min_d2, pop_back) the same on the resident distance field: cubes stop at voxels
 //     closer to an obstacle than the floor (direct_cluster_cube_corridor_clear_batch)
+//   * clusterCorridorBatch(gridPaths, corridors, pop_back) the corridors of corridorGenerationBatch / corridorInsertGenerationBatch
+//     from empty corridors with the walk itself on the device (direct_cluster_corridor_batch): due seeds de-duplicated per round,
+//     no plane read back between rounds
 //   * buildFreeComponents(min_d2) / reachable(starts, goals) which goals can be reached at all, before any path call runs
 //     (direct_cluster_free_components, direct_cluster_reachable_batch)
 // Corridor / Polytope types are template parameters read through the member names of
@@ -294,6 +297,69 @@ class polyhedronGenerator {
   }
   bool lastTableBuilt() const { return table_built_; }
 
+  // corridorGenerationBatch / corridorInsertGenerationBatch from empty corridors with the WALK ON THE DEVICE
+  // (direct_cluster_corridor_batch): the generator's own itr_inflate_max / itr_cluster_max, the due seeds of a round
+  // de-duplicated by voxel, no plane read back between rounds.  corridors[p] is filled as walk() fills it (planes, center,
+  // seed_coord), bit for bit, also where the walk stops early (the polytopes held so far); the plane capacity is
+  // getConvexPolyBatch's 128.  Returns, per path, whether the walk completed; an empty path is left without polytopes and
+  // reported false.  lastRounds() / lastPolytopes() / lastUniqueSeeds() describe the call afterwards.
+  template <class Corridor>
+  std::vector<bool> clusterCorridorBatch(const std::vector<std::vector<std::array<double, 3>>>& gridPaths,
+                                         const std::vector<Corridor*>& corridors, bool pop_back = true) {
+    if (!has_map_) throw std::runtime_error("polyhedronGenerator: no map");
+    const size_t np = gridPaths.size();
+    std::vector<bool> ok(np, false);
+    if (np == 0) return ok;
+    size_t cap = 1;
+    for (const auto& p : gridPaths) cap = std::max(cap, p.size());
+    std::vector<int32_t> xyz(np * cap * 3, 0), len(np);
+    for (size_t p = 0; p < np; p++) {
+      len[p] = (int32_t)gridPaths[p].size();
+      for (size_t i = 0; i < gridPaths[p].size(); i++) {
+        const std::array<int, 3> idx = coord2Index(gridPaths[p][i]);
+        for (int a = 0; a < 3; a++) xyz[(p * cap + i) * 3 + a] = idx[a];
+      }
+    }
+    const int pcap = 128;
+    direct_cluster_corridor_in_t in{};
+    in.batch = (int32_t)np; in.path_capacity = (int32_t)cap; in.mem_in = DIRECT_MEM_HOST;
+    in.itr_inflate_max = itr_inflate_; in.itr_cluster_max = itr_cluster_;
+    in.path_xyz = xyz.data(); in.path_len = len.data(); in.pop_back = pop_back ? 1 : 0;
+    in.seg_capacity = (int32_t)cap;  // a corridor has at most one polytope per path point: no row can overflow
+    in.p_max = pcap; in.plane_dtype = DIRECT_F64; in.resolution = res_;
+    for (int a = 0; a < 3; a++) in.map_lower[a] = lower_[a];
+    const size_t segs = np * cap;
+    std::vector<int32_t> n_seg(np), n_planes(segs), rtn(np);
+    std::vector<double> planes(segs * pcap * 4), seeds(segs * 3), centers(segs * 3);
+    direct_cluster_corridor_out_t out{};
+    out.mem = DIRECT_MEM_HOST; out.n_seg = n_seg.data(); out.n_planes = n_planes.data(); out.planes = planes.data();
+    out.seeds = seeds.data(); out.centers = centers.data(); out.rtn = rtn.data();
+    int64_t stats[4] = {0, 0, 0, 0};
+    if (direct_cluster_corridor_batch(h_, &in, &out, stats) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    rounds_ = (int)stats[0];
+    polytopes_ = (int)stats[1];
+    unique_seeds_ = (int)stats[2];
+    for (size_t p = 0; p < np; p++) {
+      ok[p] = rtn[p] == DIRECT_CORRIDOR_OK;
+      Corridor& cor = *corridors[p];
+      for (int k = 0; k < n_seg[p]; k++) {
+        const size_t at = p * cap + (size_t)k;
+        typename std::decay<decltype(cor.polyhedrons[0])>::type pt{};
+        for (int j = 0; j < n_planes[at]; j++) {
+          const double* pl = &planes[(at * pcap + j) * 4];
+          pt.appendPlane({pl[0], pl[1], pl[2], pl[3]});
+        }
+        for (int a = 0; a < 3; a++) {
+          set_elem(pt.center, a, centers[at * 3 + a]);
+          set_elem(pt.seed_coord, a, seeds[at * 3 + a]);
+        }
+        cor.polyhedrons.push_back(pt);
+      }
+    }
+    return ok;
+  }
+  int lastUniqueSeeds() const { return unique_seeds_; }  // seeds the last clusterCorridorBatch generated (lastPolytopes(): those due)
+
  private:
   // The two cube corridor calls: call(in, out) is the device call.
   template <class Corridor, class Call>
@@ -454,7 +520,7 @@ class polyhedronGenerator {
   int mx_, my_, mz_, itr_inflate_, itr_cluster_, max_batch_;
   direct_cluster_handle_t h_ = nullptr;
   bool has_map_ = false, table_built_ = false;
-  int rounds_ = 0, polytopes_ = 0;
+  int rounds_ = 0, polytopes_ = 0, unique_seeds_ = 0;
   int comp_min_d2_ = 0;  // the floor of the last buildFreeComponents
 };
 

@@ -731,14 +731,99 @@ typedef struct {
 direct_status_t direct_cluster_reachable_batch(direct_cluster_handle_t h, const direct_reachable_in_t* in,
                                                direct_reachable_out_t* out);
 
+/* ---- cluster corridors: the corridors of a batch of grid paths with is_cluster_on == true, the walk on the device ---------
+ * The cluster-mode twin of direct_cluster_cube_corridor_batch: the corridor the reference ships (inflate, cluster, hull), for many
+ * grid paths at once, written in the layout direct_ddp_batch_in_t reads (planes, n_planes, seeds: pass them on with T0 == NULL).
+ * It replaces the lock-step walk on the host (polyhedronGenerator::walk of direct_amd/host/poly_utils.hpp), which pays one host
+ * round trip per polytope of the longest corridor and reads every plane back to test the next point against it.
+ *   Result   per row, bit for bit what that walk produces (poly_utils.cpp:508-557 / :391-449), with getConvexPoly(seed) =
+ *            direct_cluster_polygon_generation_batch(seed, itr_inflate_max, itr_cluster_max) + direct_cluster_hull_planes_batch on
+ *            the resident cluster with a plane capacity of p_max.  A point is handled in this order: cur = index * resolution +
+ *            0.5 * resolution + map_lower per axis (index2Coord); a point equal to the one visited before it is skipped; with
+ *            pop_back a point that is not outside the last-but-one polytope removes the last one; a new polytope is due when the
+ *            corridor is empty or cur[0]*a + cur[1]*b + cur[2]*c + d > 0.01 for a plane of the latest polytope (double, left to
+ *            right, no contraction).  The plane tests always read the DOUBLE planes, never a float output.
+ *   Rounds   a row walks on the device until a polytope is due; the seeds due in a round are de-duplicated by voxel (a polytope
+ *            is a function of its seed voxel and the map alone; the owner of a voxel is the smallest row that asks for it), the
+ *            unique seeds are generated in chunks of at most max_batch, and every waiting row copies its polytope onto its own
+ *            plane stack.  No plane, cluster voxel or path point crosses to the host.  What does cross, and stays: one 32-byte
+ *            read-back per round (the number of unique seeds decides the chunks), and the generation's own liveness read-back,
+ *            one per four clustering rounds of every chunk.
+ *   The result does not depend on max_batch, on the order of the rows, on how the rows are split over calls or on the
+ *   de-duplication.
+ * batch is NOT limited by max_batch.  path_capacity, mem_in, path_xyz[batch][path_capacity][3] and path_len[batch] are exactly
+ * the outputs of the three grid-path calls, whose device arrays can be passed through.  itr_inflate_max > 0; itr_cluster_max >= 0,
+ * 0 means cubes (then the planes are those of direct_cluster_cube_corridor_batch wherever no capacity of this path is reached).
+ * pop_back: 1 corridorGeneration's walk, 0 corridorInsertGeneration's from an empty corridor (extending an existing corridor is
+ * not offered).  seg_capacity, p_max (>= 6), plane_dtype, resolution and map_lower as in the cube call.
+ * Outputs in memory kind out->mem, any may be NULL; planes, seeds and centers are double or float as plane_dtype says (float: one
+ * rounding of the double):
+ *   n_seg[batch]                          polytopes of the corridor the row returns (at most seg_capacity)
+ *   n_planes[batch][seg_capacity]
+ *   planes[batch][seg_capacity][p_max][4] plane rows from a polytope's n_planes on are zero
+ *   seeds[batch][seg_capacity][3], centers[batch][seg_capacity][3]
+ *   rtn[batch]                            codes below, per row: a failing row never affects another
+ * Every entry from a row's n_seg on is zero, n_planes included.
+ * stats (HOST, [4] or NULL), all deterministic: [0] rounds in which a seed was due (the rounds of the lock-step walk), [1] due
+ * seeds summed over the rounds, [2] unique seeds actually generated, [3] pops.
+ * DIRECT_ERR_INVALID, nothing launched: what the cube call refuses (a handle without a map; a NULL handle, struct, path_xyz or
+ * path_len; a non-positive batch, path_capacity, seg_capacity or itr_inflate_max; p_max < 6; an unknown mem_in, mem or
+ * plane_dtype; a resolution that is not finite and positive; a non-finite map_lower) and a negative itr_cluster_max.
+ * DIRECT_ERR_UNSUPPORTED: batch * path_capacity or batch * seg_capacity * p_max of 2^28 or more.  DIRECT_ERR_DEVICE: a device
+ * error, or rows still walking after path_capacity + 1 rounds (every unfinished row ends or consumes a point per round, so this
+ * bound cannot be reached; it is checked, never spun on).
+ * STATE.  The call uses the handle's cluster storage: it INVALIDATES resident clusters, as direct_cluster_convex_test does (a
+ * following direct_cluster_hull_planes_batch with cluster_xyz == NULL fails until the next generation).  It leaves the map and
+ * its table, the grid-path workspace, the distance field, the floor tables and the free components alone.  It runs on the
+ * handle's stream and synchronises before it returns.  direct_cluster_last_ms covers the call from its first kernel to its last,
+ * which INCLUDES the waits of its small read-backs (not the copies of host arrays).  Its workspace (64 B per row, the double
+ * plane stack of 32 B x batch x seg_capacity x p_max with 52 B per polytope slot beside it, 4 B per voxel for the owner table,
+ * the hull outputs of one chunk) and the staging of host arrays are blocks of its own on the handle, grown on demand, never
+ * shrunk and freed in direct_cluster_destroy. */
+#define DIRECT_CORRIDOR_OK 0
+#define DIRECT_CORRIDOR_OVERFLOW 1         /* the walk needed polytope seg_capacity + 1 and stopped there: n_seg = seg_capacity, and those polytopes are the stack at that moment - later points could have popped some of them, so they need not be a prefix of the full corridor */
+#define DIRECT_CORRIDOR_BAD_PATH 2         /* path_len <= 0, path_len > path_capacity (an OVERFLOW row of the path stage), or a voxel outside the map: n_seg 0 */
+#define DIRECT_CORRIDOR_NO_POLYTOPE 3      /* the generation of a due seed did not end DIRECT_CLUSTER_OK or its hull did not end DIRECT_HULL_OK (the reference's cdd-error branch): the walk stops, n_seg is the polytopes held so far, as walk() leaves them */
+#define DIRECT_CORRIDOR_TOO_MANY_PLANES 4  /* a polytope has more than p_max facets: the walk stops in the same way */
+typedef struct {
+  int32_t batch, path_capacity;
+  int32_t mem_in;            /* direct_mem_t of path_xyz and path_len */
+  int32_t itr_inflate_max;   /* > 0; paramSet's value is 1000 */
+  const int32_t* path_xyz;   /* [batch][path_capacity][3] */
+  const int32_t* path_len;   /* [batch] */
+  int32_t itr_cluster_max;   /* >= 0; 0: cubes */
+  int32_t pop_back;          /* 1: corridorGeneration's walk, 0: corridorInsertGeneration's from an empty corridor */
+  int32_t seg_capacity;
+  int32_t p_max;             /* >= 6 */
+  int32_t plane_dtype;       /* direct_dtype_t of planes, seeds, centers */
+  int32_t reserved;
+  double resolution;
+  double map_lower[3];
+} direct_cluster_corridor_in_t;
+
+typedef struct {
+  int32_t mem;               /* direct_mem_t: where every array below lives */
+  int32_t reserved;
+  int32_t* n_seg;            /* [batch] or NULL */
+  int32_t* n_planes;         /* [batch][seg_capacity] or NULL */
+  void* planes;              /* [batch][seg_capacity][p_max][4] or NULL */
+  void* seeds;               /* [batch][seg_capacity][3] or NULL */
+  void* centers;             /* [batch][seg_capacity][3] or NULL */
+  int32_t* rtn;              /* [batch] or NULL */
+} direct_cluster_corridor_out_t;
+
+direct_status_t direct_cluster_corridor_batch(direct_cluster_handle_t h, const direct_cluster_corridor_in_t* in,
+                                              direct_cluster_corridor_out_t* out, int64_t* stats /* HOST [4] or NULL */);
+
 /* The HIP stream (hipStream_t) the handle enqueues its copies, kernels and timing events on; NULL (the default) is
  * the legacy default stream.  Mirrors direct_ddp_set_stream. */
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
  * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch /
- * grid_path_clear_batch / grid_path_fan_batch / free_components / reachable_batch call (the fan: its init, bounds, rounds,
- * read-back and stats kernels with the read-backs of the round counters between them, not the copies of host arrays; the
- * components: the two clears and the four kernels of a build, the one kernel of reachable_batch) */
+ * grid_path_clear_batch / grid_path_fan_batch / free_components / reachable_batch / corridor_batch call (the fan: its init,
+ * bounds, rounds, read-back and stats kernels with the read-backs of the round counters between them, not the copies of host
+ * arrays; the components: the two clears and the four kernels of a build, the one kernel of reachable_batch; corridor_batch:
+ * from its first kernel to its last, the waits of its read-backs included) */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
 #ifdef __cplusplus
