@@ -21,6 +21,12 @@ class MapCloud(C.Structure):  # direct_map_cloud_t
                 ("reserved", C.c_int32)]
 
 
+class MapScan(C.Structure):  # direct_map_scan_t
+    _fields_ = [("map_lower", C.c_double * 3), ("map_upper", C.c_double * 3), ("resolution", C.c_double), ("max_range", C.c_double),
+                ("origin", C.c_double * 3), ("inflate", C.c_int32 * 3), ("mode", C.c_int32), ("stride", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class PlanCheckIn(C.Structure):  # direct_plan_check_in_t
     _fields_ = [("batch", C.c_int32), ("n_seg_max", C.c_int32), ("mem", C.c_int32), ("dtype", C.c_int32), ("n_seg", C.c_void_p),
                 ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p), ("map_lower", C.c_double * 3), ("resolution", C.c_double),
@@ -47,12 +53,15 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_distance_field", "direct_cluster_get_distance_field", "direct_cluster_plan_clearance_batch",
            "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch",
            "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
-           "direct_cluster_reachable_batch", "direct_cluster_corridor_batch")
+           "direct_cluster_reachable_batch", "direct_cluster_corridor_batch", "direct_cluster_map_integrate_scan",
+           "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
 MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
+SCAN_RESET, SCAN_CONTINUE, SCAN_ADOPT = 0, 1, 2
+SCAN_STATS = ("points", "skipped_nonfinite", "truncated", "outside", "raw_occupied", "occupied", "set", "cleared")   # stats[8]
 PLAN_CHECK_INVALID = -1
 DIST_NONE = 0x7fffffff
 CUBE_CORRIDOR_OK, CUBE_CORRIDOR_OVERFLOW, CUBE_CORRIDOR_BAD_PATH = 0, 1, 2
@@ -93,6 +102,9 @@ def _lib():
         L.direct_cluster_get_free_components.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_reachable_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_corridor_batch.argtypes = list(abi.CLUSTER_CORRIDOR_ARGTYPES)
+        L.direct_cluster_map_integrate_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.direct_cluster_get_scan_grid.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_scan_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -148,6 +160,16 @@ class ClusterGenerator:
         upper = lower + np.asarray(self.dims, np.float64) * float(resolution) if map_upper is None else np.asarray(map_upper, np.float64).reshape(3)
         par = MapCloud((C.c_double * 3)(*lower), (C.c_double * 3)(*upper), float(resolution), float(cloud_margin),
                        {"clamp": MAP_BORDER_CLAMP, "drop": MAP_BORDER_DROP}[border], MAP_ADD if add else MAP_REPLACE, 0, 0)
+        pts, mem, ptr = self._cloud(points)
+        par.stride = int(pts.shape[1])
+        n = int(pts.shape[0])
+        stats = np.zeros(4, np.int64)
+        _check(_lib().direct_cluster_map_from_cloud(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
+        return dict(points=int(stats[0]), skipped_nonfinite=int(stats[1]), dropped=int(stats[2]), occupied=int(stats[3]))
+
+    @staticmethod
+    def _cloud(points):
+        """-> (the array or tensor that owns the floats, mem, pointer) of a cloud given as NumPy or as a device tensor"""
         if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
             pts = np.ascontiguousarray(points, np.float32)
             pts = pts.reshape(0, 3) if pts.size == 0 and pts.ndim != 2 else pts
@@ -159,11 +181,38 @@ class ClusterGenerator:
             torch.cuda.current_stream(pts.device).synchronize()  # the handle's stream is not torch's
             mem, ptr = abi.MEM_DEVICE, pts.data_ptr()
         assert pts.ndim == 2 and pts.shape[1] in (3, 4), "points must have shape [n, 3] or [n, 4]"
-        par.stride = int(pts.shape[1])
+        return pts, mem, ptr
+
+    def integrate_scan(self, points, origin, map_lower, resolution, max_range, inflate=(0, 0, 0), mode="continue", map_upper=None):
+        """One sensor scan folded into the resident map (direct_cluster_map_integrate_scan): every ray from origin to a point
+        carves the scan grid free, every return within max_range marks its voxel, and the map is the scan grid dilated by the
+        voxel box inflate.  points as in set_map_from_cloud.  mode: "reset" (the scan grid starts empty), "continue" (keep it) or
+        "adopt" (it starts as the map the handle holds).  The field, the floor tables and the components stay valid when
+        set + cleared == 0; rebuild them otherwise.
+        -> dict(points, skipped_nonfinite, truncated, outside, raw_occupied, occupied, set, cleared)"""
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        upper = lower + np.asarray(self.dims, np.float64) * float(resolution) if map_upper is None else np.asarray(map_upper, np.float64).reshape(3)
+        pts, mem, ptr = self._cloud(points)
+        par = MapScan((C.c_double * 3)(*lower), (C.c_double * 3)(*upper), float(resolution), float(max_range),
+                      (C.c_double * 3)(*np.asarray(origin, np.float64).reshape(3)), (C.c_int32 * 3)(*[int(v) for v in inflate]),
+                      {"reset": SCAN_RESET, "continue": SCAN_CONTINUE, "adopt": SCAN_ADOPT}[mode], int(pts.shape[1]), 0)
         n = int(pts.shape[0])
-        stats = np.zeros(4, np.int64)
-        _check(_lib().direct_cluster_map_from_cloud(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
-        return dict(points=int(stats[0]), skipped_nonfinite=int(stats[1]), dropped=int(stats[2]), occupied=int(stats[3]))
+        stats = np.zeros(8, np.int64)
+        _check(_lib().direct_cluster_map_integrate_scan(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
+        return dict(zip(SCAN_STATS, (int(v) for v in stats)))
+
+    def scan_grid(self):
+        """The scan grid as a uint8 array of shape dims (direct_cluster_get_scan_grid): what the scans so far carved and marked,
+        before the inflation"""
+        g = np.zeros(self.dims, np.uint8)
+        _check(_lib().direct_cluster_get_scan_grid(self.h, abi.MEM_HOST, g.ctypes.data))
+        return g
+
+    def scan_phase_ms(self):
+        """[carve, mark, inflate, table] ms of the last scan; the handle must have been created with DIRECT_CLUSTER_SCAN_TIMING=1"""
+        ms = (C.c_float * 4)()
+        _check(_lib().direct_cluster_scan_phase_ms(self.h, ms))
+        return [float(v) for v in ms]
 
     def get_map(self):
         """The handle's map as a uint8 array of shape dims (direct_cluster_get_map)"""

@@ -995,6 +995,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "cube_corridor_clear.h"
 #include "free_comp.h"
 #include "cluster_corridor.h"
+#include "map_scan.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1056,6 +1057,14 @@ struct direct_cluster_handle_s {
   hs::Block reach_in, reach_out;  // device staging of reachable_batch's host inputs / host outputs, grown on demand
   hs::Block corr_ws;   // workspace of corridor_batch (walk states, plane stacks, owner table, seed list, a chunk's hull outputs), grown on demand
   hs::Block corr_in, corr_out;  // device staging of its host inputs / host outputs, grown on demand
+  uint8_t* scan_raw = nullptr;            // the scan grid of map_integrate_scan (the map's size and layout), allocated by its first call
+  unsigned long long* scan_cnt = nullptr; // [kScanCounters] its counters
+  bool have_scan = false;                 // scan_raw holds what the scans so far left
+  hs::Block scan_ws;                      // the two intermediate grids of its inflation, grown by the first call that inflates in y or z
+  bool scan_test_store = true;            // the carve loads a byte before it stores (DIRECT_CLUSTER_SCAN_STORE=plain: experiments)
+  bool scan_timing = false;               // record the phases' events (DIRECT_CLUSTER_SCAN_TIMING=1: tools/map_scan_bench.py)
+  hipEvent_t scan_ev[5] = {};             // before the carve, behind the carve, the mark, the inflation and the table
+  float scan_ms[4] = {0, 0, 0, 0};        // what they measured in the last call (the table: 0 when it was not rebuilt)
 };
 
 namespace {
@@ -1408,6 +1417,8 @@ direct_status_t direct_cluster_create(const direct_cluster_config_t* cfg, direct
   direct_cluster_handle_t h = new direct_cluster_handle_s();
   h->cfg = *cfg;
   if (const char* ev = getenv("DIRECT_CLUSTER_CONVEX_GRID")) h->convex_grid = atoi(ev) > 0 ? atoi(ev) : h->convex_grid;
+  if (const char* ev = getenv("DIRECT_CLUSTER_SCAN_STORE")) h->scan_test_store = std::string(ev) != "plain";
+  if (const char* ev = getenv("DIRECT_CLUSTER_SCAN_TIMING")) h->scan_timing = atoi(ev) > 0;
   if (const char* ev = getenv("DIRECT_CLUSTER_FAN_BOUND_EVERY")) h->fan_bound_every = atoi(ev) == gp::kFanRoundsPerCheck ? gp::kFanRoundsPerCheck : 1;
   Dev& D = h->D;
   D.max_x = cfg->max_x; D.max_y = cfg->max_y; D.max_z = cfg->max_z; D.max_yz = cfg->max_y * cfg->max_z;
@@ -1452,8 +1463,10 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
-                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out})
+                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out, &h->scan_ws})
     hs::release(*b);
+  for (hipEvent_t e : h->scan_ev)
+    if (e) (void)hipEventDestroy(e);
   hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
@@ -1543,6 +1556,134 @@ direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, u
   CHIP_TRY(hipMemcpyAsync(map_data, h->map, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
                           h->stream));
   CHIP_TRY(hipStreamSynchronize(h->stream));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem,
+                                                  const float* xyz, int64_t* stats) {
+  if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (p->mode != DIRECT_SCAN_RESET && p->mode != DIRECT_SCAN_CONTINUE && p->mode != DIRECT_SCAN_ADOPT) return cfail(DIRECT_ERR_INVALID, "unknown mode");
+  if (p->stride != 3 && p->stride != 4) return cfail(DIRECT_ERR_INVALID, "stride must be 3 or 4 floats per point");
+  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  if (!std::isfinite(p->max_range) || !(p->max_range > 0.0)) return cfail(DIRECT_ERR_INVALID, "max_range must be finite and positive");
+  for (int a = 0; a < 3; a++) {
+    if (!std::isfinite(p->map_lower[a]) || !std::isfinite(p->map_upper[a])) return cfail(DIRECT_ERR_INVALID, "map_lower / map_upper must be finite");
+    if (p->inflate[a] < 0) return cfail(DIRECT_ERR_INVALID, "inflate must not be negative");
+  }
+  const Dev& D = h->D;
+  ScanDev S = {};
+  ms::Grid& G = S.G;
+  G.resolution = p->resolution; G.inv = 1.0 / p->resolution; G.R2 = p->max_range * p->max_range;
+  G.size[0] = D.max_x; G.size[1] = D.max_y; G.size[2] = D.max_z;
+  for (int a = 0; a < 3; a++) {
+    G.lower[a] = p->map_lower[a]; G.origin[a] = p->origin[a];
+    G.start[a] = mc::axis_index_drop(p->origin[a], p->map_lower[a], p->map_upper[a], G.inv, G.size[a]);  // -1 for a NaN too
+    if (G.start[a] < 0) return cfail(DIRECT_ERR_INVALID, "the origin lies outside the map");
+  }
+  if (p->mode == DIRECT_SCAN_ADOPT && !h->have_map) return cfail(DIRECT_ERR_INVALID, "DIRECT_SCAN_ADOPT: the handle has no map");
+  if (!(p->max_range * G.inv <= (double)ms::kMaxRangeVox)) return cfail(DIRECT_ERR_UNSUPPORTED, "max_range above 4096 voxels");
+  for (int a = 0; a < 3; a++)
+    if (p->inflate[a] > ms::kMaxInflate) return cfail(DIRECT_ERR_UNSUPPORTED, "inflate above 64 voxels");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)D.G;
+  if (!h->scan_raw)
+    CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->scan_raw, cells), hs::want(&h->scan_cnt, kScanCounters * sizeof(unsigned long long))}));
+  if (h->scan_timing && !h->scan_ev[0])
+    for (hipEvent_t& e : h->scan_ev) CHIP_TRY(hipEventCreate(&e));
+  S.n = n_points; S.stride = p->stride; S.raw = h->scan_raw; S.cnt = h->scan_cnt;
+  if (p->inflate[1] > 0 || p->inflate[2] > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, 2 * cells));
+  const size_t bytes = (size_t)n_points * p->stride * sizeof(float);
+  if (mem == DIRECT_MEM_HOST && n_points > 0) {
+    CHIP_TRY(hs::grow(h->cloud_in, h->stream, bytes));
+    CHIP_TRY(hipMemcpyAsync(h->cloud_in.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+    S.xyz = (const float*)h->cloud_in.p;
+  } else {
+    S.xyz = xyz;
+  }
+  const bool had_map = h->have_map;
+  auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->scan_ev[k], h->stream) : hipSuccess; };
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(h->scan_cnt, 0, kScanCounters * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess && !had_map) e = hipMemsetAsync(h->map, 0, cells, h->stream);  // the bytes "before" of a handle without a map
+  if (e == hipSuccess) {
+    if (p->mode == DIRECT_SCAN_ADOPT) e = hipMemcpyAsync(h->scan_raw, h->map, cells, hipMemcpyDeviceToDevice, h->stream);
+    else if (p->mode == DIRECT_SCAN_RESET || !h->have_scan) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
+  }
+  h->have_scan = false;  // until the call has ended well
+  const int ray_blocks = (int)std::min<long long>((n_points + 255) / 256, kScanMaxBlocks);
+  if (e == hipSuccess) e = tick(0);
+  if (e == hipSuccess && n_points > 0) {
+    if (h->scan_test_store) hipLaunchKernelGGL(k_scan_carve<true>, dim3(ray_blocks), dim3(256), 0, h->stream, S);
+    else hipLaunchKernelGGL(k_scan_carve<false>, dim3(ray_blocks), dim3(256), 0, h->stream, S);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(1);
+  if (e == hipSuccess && n_points > 0) {
+    hipLaunchKernelGGL(k_scan_mark, dim3(ray_blocks), dim3(256), 0, h->stream, S);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(2);
+  if (e == hipSuccess) {  // z, then y, through the workspace where they inflate at all; x last, into the map
+    DilateDev P = {};
+    for (int a = 0; a < 3; a++) P.size[a] = G.size[a];
+    P.G = (long long)cells; P.cnt = h->scan_cnt; P.src = h->scan_raw;
+    const int blocks = (int)std::min<long long>(((long long)cells + 255) / 256, kScanMaxBlocks);
+    for (int axis = 2; axis >= 0; axis--) {
+      if (axis > 0 && p->inflate[axis] == 0) continue;
+      P.axis = axis; P.r = p->inflate[axis];
+      P.dst = axis == 0 ? h->map : (uint8_t*)h->scan_ws.p + (axis == 2 ? 0 : cells);
+      P.raw = axis == 0 ? h->scan_raw : nullptr;
+      hipLaunchKernelGGL(k_scan_dilate, dim3(blocks), dim3(256), 0, h->stream, P);
+      P.src = P.dst;
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(3);
+  unsigned long long cnt[kScanCounters] = {};
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt, h->scan_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, e);
+  const bool changed = !had_map || cnt[kScanSet] + cnt[kScanCleared] > 0;
+  if (e == hipSuccess && changed) e = rebuild_sat(h);  // nothing changed: the table, the field, the floor tables and the labels stay
+  if (e == hipSuccess) e = tick(4);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e == hipSuccess && h->scan_timing)
+    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&h->scan_ms[k], h->scan_ev[k], h->scan_ev[k + 1]);
+  if (e != hipSuccess) {  // the map and the scan grid have been touched: nothing describes them any more
+    h->have_map = false;
+    h->dist_valid = false;
+    h->map_gen++;
+    return cfail(DIRECT_ERR_DEVICE, std::string("map_integrate_scan: ") + hipGetErrorString(e));
+  }
+  if (changed) {
+    h->dist_valid = false;
+    h->map_gen++;
+  }
+  h->have_map = true;
+  h->have_scan = true;
+  if (stats) {
+    stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
+    stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
+  }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_scan_grid(direct_cluster_handle_t h, int32_t mem, uint8_t* raw) {
+  if (!h || !raw) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!h->have_scan) return cfail(DIRECT_ERR_INVALID, "the handle has no scan grid");
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  CHIP_TRY(hipMemcpyAsync(raw, h->scan_raw, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_scan_phase_ms(direct_cluster_handle_t h, float* ms4) {
+  if (!h || !ms4) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!h->scan_timing || !h->have_scan) return cfail(DIRECT_ERR_INVALID, "no timed scan: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
+  for (int k = 0; k < 4; k++) ms4[k] = h->scan_ms[k];
   return DIRECT_OK;
 }
 

@@ -81,6 +81,44 @@ class polyhedronGenerator {
     return stats[3];
   }
 
+  // One sensor scan folded into the map the generator holds (direct_cluster_map_integrate_scan): every ray from origin to a point
+  // carves the scan grid free, every return within max_range marks its voxel, and the map is the scan grid dilated by the voxel
+  // box inflate (zeros for the radius-aware calls; the radius in voxels for the corridors, which have no floor).  mode:
+  // DIRECT_SCAN_RESET, DIRECT_SCAN_CONTINUE, or DIRECT_SCAN_ADOPT after setMap / setCloud.  Unlike setCloud(add = true) a voxel
+  // that a later ray passes leaves the map again.  changed() == false: the distance field and the free components still serve.
+  struct ScanResult {
+    long long points = 0, skipped_nonfinite = 0, truncated = 0, outside = 0, raw_occupied = 0, occupied = 0, set = 0, cleared = 0;
+    bool changed() const { return set + cleared > 0; }
+  };
+  ScanResult integrateScan(const float* xyz, int64_t n, int stride, const std::array<double, 3>& origin, double max_range,
+                           const std::array<int, 3>& inflate = {{0, 0, 0}}, int mode = DIRECT_SCAN_CONTINUE) {
+    direct_map_scan_t p{};
+    for (int a = 0; a < 3; a++) {
+      p.map_lower[a] = lower_[a];
+      p.map_upper[a] = lower_[a] + (a == 0 ? mx_ : (a == 1 ? my_ : mz_)) * res_;
+      p.origin[a] = origin[a];
+      p.inflate[a] = inflate[a];
+    }
+    p.resolution = res_;
+    p.max_range = max_range;
+    p.mode = mode;
+    p.stride = stride;
+    int64_t s[8];
+    if (direct_cluster_map_integrate_scan(h_, &p, n, DIRECT_MEM_HOST, xyz, s) != DIRECT_OK)
+      throw std::runtime_error(direct_cluster_last_error());
+    has_map_ = true;
+    ScanResult r;
+    r.points = s[0]; r.skipped_nonfinite = s[1]; r.truncated = s[2]; r.outside = s[3];
+    r.raw_occupied = s[4]; r.occupied = s[5]; r.set = s[6]; r.cleared = s[7];
+    return r;
+  }
+  // the map as the generator holds it, [x][y][z] (direct_cluster_get_map)
+  std::vector<uint8_t> getMap() {
+    std::vector<uint8_t> m((size_t)mx_ * my_ * mz_);
+    if (direct_cluster_get_map(h_, DIRECT_MEM_HOST, m.data()) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return m;
+  }
+
   // One plan against the map the generator holds NOW (direct_cluster_plan_check_batch): polyCoeff(k, q) and time(k) as
   // getPolyCoeff() / getPolyTime() give them (Eigen matrices or anything with the same call operators and time.size()).  Conservative:
   // a blocked verdict means that a piece of the curve of duration T_i / 2^depth has a bounding box touching an occupied voxel, not

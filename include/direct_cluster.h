@@ -826,6 +826,71 @@ direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_s
  * from its first kernel to its last, the waits of its read-backs included) */
 direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 
+/* ---- one sensor scan folded into the map: carve the free space, mark the returns ------------------------------------
+ * direct_cluster_map_from_cloud can forget everything (REPLACE) or never forget anything (ADD).  This call uses the other half
+ * of a range measurement: the ray from the sensor to a return is empty.  A spurious return, a door that has opened or a person
+ * who has walked on leaves the map with the next scan that looks through the place.  There is no reference counterpart (the
+ * reference builds its map once); the definition below is this library's own and is restated by tests/map_scan_harness.py.
+ * The handle keeps a second resident grid, the SCAN GRID `raw`: the map's size and layout, bytes 0 or 1, allocated by the
+ * first call.  One call is one scan, four steps in order:
+ *   1. Carve    every ray from `origin` to a point writes 0 into the raw voxels it passes (the walk below).
+ *   2. Mark     every HIT ray writes 1 into the raw voxel of its point.  All carving precedes all marking, and each phase
+ *               writes one byte value only: the result depends neither on the order of the points nor on the launch shape, and
+ *               the returns of this scan always survive it.
+ *   3. Inflate  map[x,y,z] = 1 exactly when some raw voxel with |dx| <= inflate[0], |dy| <= inflate[1], |dz| <= inflate[2]
+ *               INSIDE the map is 1: a voxel box, no wrap; inflate = {0,0,0} makes the map equal raw.  This is deliberately NOT
+ *               the coordinate inflation of direct_cluster_map_from_cloud: dilating raw is what lets a carved voxel take its
+ *               shell with it.  Callers of the radius-aware calls (min_d2, radius) pass zeros; callers of
+ *               direct_cluster_corridor_batch, which has no floor, pass their radius in voxels.
+ *   4. Tables   while the map is written, the voxels that change 0 -> 1 and 1 -> 0 are counted against the bytes the map held
+ *               before the call, whoever wrote them.  If anything changed, or the handle had no map, the call has
+ *               direct_cluster_set_map's effect on everything the handle holds (the summed-area table is rebuilt by the same
+ *               code; the distance field, the floor tables and the free components are stale; resident clusters stay).  If
+ *               NOTHING changed, all of them stay valid and nothing is rebuilt: a node that scans a static room at 10 Hz pays
+ *               for no field.  Rebuild the field when stats[6] + stats[7] > 0.
+ * Unknown space is not tracked: a voxel never seen is free, as in the reference.  There is no hit counting and no log-odds:
+ * the last observation wins.  Both are out of scope.
+ * The walk.  All in double, no square root; inv = 1.0 / resolution and R2 = max_range * max_range computed once on the host;
+ * e_a = (double)p_a, d_a = e_a - origin_a, dd = (d_x*d_x + d_y*d_y) + d_z*d_z without fused multiply-adds.  A ray is a HIT when
+ * dd <= R2, otherwise TRUNCATED: it carves out to max_range and marks nothing.  Start voxel i: the origin's, by the DROP rule of
+ * direct_cluster_map_from_cloud.  End voxel of a hit: j_a = (int)floor((e_a - map_lower_a) * inv), inside when 0 <= j_a < size_a
+ * for all a.  Per axis step_a = sign(d_a), n_a = |j_a - i_a| for a hit, and for step_a != 0: b = map_lower_a + (double)(i_a +
+ * (step_a > 0)) * resolution, tmax_a = (b - origin_a) / d_a, tdel_a = resolution / fabs(d_a).  Loop: stop without writing when
+ * the current voxel is outside the map; a hit stops when n_x + n_y + n_z steps are done; choose the axis with the smallest tmax
+ * among those with step != 0 and, for a hit, n_a > 0 (ties: the lower axis); clear the current voxel; a truncated ray stops here
+ * when !((t*t)*dd <= R2) for the chosen t = tmax_a; then i_a += step_a, tmax_a += tdel_a, n_a -= 1.  A hit clears every voxel
+ * before j and ends in j exactly, by counting; a truncated ray clears its last voxel too.  A point with a non-finite coordinate
+ * contributes nothing.
+ * xyz[n_points][stride] floats in memory kind `mem`.  stats (host [8], may be NULL): [0] points read, [1] points skipped as
+ * non-finite, [2] truncated rays, [3] hits whose voxel lies outside the map (no mark), [4] raw voxels at 1 after the call,
+ * [5] map voxels at 1 after the call, [6] map voxels that went 0 -> 1, [7] map voxels that went 1 -> 0.
+ * DIRECT_ERR_INVALID (the handle is left as it was): null handle or parameters; n_points < 0; xyz == NULL with n_points > 0; an
+ * unknown mem, mode or stride; a resolution or max_range that is not finite and positive; a non-finite map_lower or map_upper;
+ * an origin outside [map_lower, map_upper) or beyond the last voxel; a negative inflate; ADOPT without a map.
+ * DIRECT_ERR_UNSUPPORTED: max_range * inv above 4096; an inflate above 64.  n_points == 0 is legal: RESET then gives an empty map.
+ * After DIRECT_ERR_DEVICE the handle has neither a map nor a scan grid.
+ * Runs on the handle's stream and synchronises before it returns; direct_cluster_last_ms covers the clears, the kernels, the
+ * wait for the counters and the table (not the copy of a host cloud).  The scan grid (1 B per voxel) lives as long as the
+ * handle; the two intermediate grids of an inflation in y or z are a block of their own, grown on demand. */
+#define DIRECT_SCAN_RESET    0  /* the scan grid starts empty */
+#define DIRECT_SCAN_CONTINUE 1  /* keep it; a handle without one starts empty */
+#define DIRECT_SCAN_ADOPT    2  /* the scan grid starts as the bytes of the map the handle holds (INVALID without a map) */
+typedef struct {
+  double map_lower[3], map_upper[3];
+  double resolution, max_range;
+  double origin[3];
+  int32_t inflate[3];
+  int32_t mode, stride /* 3 or 4 */, reserved;
+} direct_map_scan_t;
+direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points,
+                                                  int32_t mem, const float* xyz, int64_t* stats /* host [8] or NULL */);
+/* The scan grid, raw[max_x*max_y*max_z] in memory kind `mem`; DIRECT_ERR_INVALID before the first scan. */
+direct_status_t direct_cluster_get_scan_grid(direct_cluster_handle_t h, int32_t mem, uint8_t* raw);
+/* For measurements: ms4[0..3] = HIP-event time [ms] of the carve, the mark, the inflation and the table rebuild (0 when nothing
+ * changed) of the last scan.  Recorded only by a handle created with DIRECT_CLUSTER_SCAN_TIMING=1 in the environment
+ * (DIRECT_ERR_INVALID otherwise); DIRECT_CLUSTER_SCAN_STORE=plain makes the carve store without loading the byte first. */
+direct_status_t direct_cluster_scan_phase_ms(direct_cluster_handle_t h, float* ms4);
+
 #ifdef __cplusplus
 }
 #endif
