@@ -834,36 +834,77 @@ struct Wave {
     const int bi = cur + 1 + step % (B.nbuf - 1);
     return bi >= B.nbuf ? bi - B.nbuf : bi;
   }
+  // kTrajBase (float storage): the bases are those of TRAJECTORY b (its knot 0) - the one 64-bit product per array is
+  // formed here, once per sweep, and what a knot adds is a 32-bit byte offset: one s_mul_i32 and one add with carry per
+  // array and knot where the address built from (b * nmax + k) takes two 64-bit multiplies (s_mul_hi_u32), a 64-bit shift
+  // and the add, and a lane's element rides on that scalar base as an unsigned 32-bit byte offset (el) where a signed
+  // element index costs a sign extension and a 64-bit vector add per access.
+  // Double storage keeps the batch's bases and signed indices: its instantiations sit elsewhere on the register cliff, and
+  // either half of the new form alone puts a spill reload into the backward knot loop of k_iterate_dyn<double, 4, false>
+  // and two more into phase R of k_iterate<double, 4>.
+  static constexpr bool kTrajBase = sizeof(St) < sizeof(double);
+  static constexpr unsigned kSt = (unsigned)sizeof(St);
   DDP_DEV void set_sweep_ptrs(int cur, int t0 = -1, int t1 = -1) {
+    const size_t row0 = kTrajBase ? (size_t)(unsigned)DDP_UNIFORM_I(b * B.nmax) : 0;
+    const size_t xrow0 = kTrajBase ? (size_t)(unsigned)DDP_UNIFORM_I(b * (B.nmax + 1)) : 0;
+    const size_t srow0 = row0 * (unsigned)DDP_UNIFORM_I(B.ncs), prow0 = row0 * (unsigned)DDP_UNIFORM_I(B.pmax * 4);
     for (int i = 0; i < 3; i++) {
       int bi = i == 0 ? cur : (i == 1 ? t0 : t1);
       if (bi < 0) bi = cur;
       bi = DDP_UNIFORM_I(bi);
-      sp.X[i] = (GSt*)uniform_ptr(B.X[bi]);
-      sp.S[i] = (GSt*)uniform_ptr(B.S[bi]);
-      sp.Y[i] = (GSt*)uniform_ptr(B.Y[bi]);
+      sp.X[i] = (GSt*)uniform_ptr(B.X[bi]) + xrow0 * x_stride<St>();
+      sp.S[i] = (GSt*)uniform_ptr(B.S[bi]) + srow0;
+      sp.Y[i] = (GSt*)uniform_ptr(B.Y[bi]) + srow0;
       DDP_OPAQUE_S(sp.X[i]);
       DDP_OPAQUE_S(sp.S[i]);
       DDP_OPAQUE_S(sp.Y[i]);
     }
     // (uniform_ptr: in the out-of-line halves of a shared sweep the Batch is read from memory, and the compiler does not
     // take every one of these loads for wave-uniform; on kernel arguments it folds away)
-    sp.KS = (GSt*)uniform_ptr(B.KS); sp.KY = (GSt*)uniform_ptr(B.KY); sp.KU = (GSt*)uniform_ptr(B.KU);
-    sp.planes = (GCSt*)uniform_ptr(B.planes);
-    sp.n_planes = (GCInt*)uniform_ptr(B.n_planes);
+    sp.KS = (GSt*)uniform_ptr(B.KS) + srow0; sp.KY = (GSt*)uniform_ptr(B.KY) + srow0;
+    sp.KU = (GSt*)uniform_ptr(B.KU) + row0 * 100;
+    sp.planes = (GCSt*)uniform_ptr(B.planes) + prow0;
+    sp.n_planes = (GCInt*)uniform_ptr(B.n_planes) + row0;
     DDP_OPAQUE_S(sp.KS);
     DDP_OPAQUE_S(sp.KY);
     DDP_OPAQUE_S(sp.KU);
     DDP_OPAQUE_S(sp.planes);
     DDP_OPAQUE_S(sp.n_planes);
   }
-  DDP_DEV size_t rowU(int k) const { return (size_t)(unsigned)DDP_UNIFORM_I(b * B.nmax + k); }
+  // `base` + `off` BYTES, off unsigned 32-bit: a lane's load or store then takes the scalar base and its offset register
+  // as they are (the saddr form), no 64-bit vector add; on the scalar unit one add with carry
+  template <typename Ptr>
+  static DDP_DEV Ptr at_byte(Ptr base, unsigned off) {
+    return (Ptr)((DDP_GLOBAL const char*)base + off);
+  }
+  // element idx (a lane's small, non-negative index) of a knot's rows
+  template <typename Ptr>
+  static DDP_DEV auto& el(Ptr base, int idx) {
+    if constexpr (kTrajBase) return *at_byte(base, (unsigned)idx * kSt);
+    else return base[idx];
+  }
+  // Knot k (wave-uniform, >= 0) of the arrays.  kTrajBase: its byte offset in a trajectory's rows is below 2^32 for any
+  // batch the library accepts (direct_ddp_create; the widest rows, KS / KY, are nmax * ncs * sizeof(St) bytes).
   // sel: 0 = the current iterate buffer, 1 / 2 = the trial buffers
-  DDP_DEV GSt* XpU(int sel, int k) const { return sp.X[sel] + (size_t)(unsigned)DDP_UNIFORM_I(b * (B.nmax + 1) + k) * x_stride<St>(); }
-  DDP_DEV GSt* SpU(GSt* base, int k) const { return base + rowU(k) * B.ncs; }
-  DDP_DEV GCSt* planesU(int k) const { return sp.planes + rowU(k) * (B.pmax * 4); }
-  DDP_DEV int npU(int k) const { return sp.n_planes[rowU(k)]; }
-  DDP_DEV GSt* KUpU(int k) const { return sp.KU + rowU(k) * 100; }
+  DDP_DEV size_t rowU(int k) const { return (size_t)(unsigned)DDP_UNIFORM_I(b * B.nmax + k); }
+  // (one DDP_UNIFORM_I per array: the emulator checks a site's value across the lanes of a block, and the offsets differ)
+  DDP_DEV GSt* XpU(int sel, int k) const {
+    if constexpr (kTrajBase) return at_byte(sp.X[sel], (unsigned)DDP_UNIFORM_I(k * x_stride<St>()) * kSt);
+    else return sp.X[sel] + (size_t)(unsigned)DDP_UNIFORM_I(b * (B.nmax + 1) + k) * x_stride<St>();
+  }
+  DDP_DEV GSt* SpU(GSt* base, int k) const {
+    if constexpr (kTrajBase) return at_byte(base, (unsigned)DDP_UNIFORM_I(k * B.ncs) * kSt);
+    else return base + rowU(k) * B.ncs;
+  }
+  DDP_DEV GCSt* planesU(int k) const {
+    if constexpr (kTrajBase) return at_byte(sp.planes, (unsigned)DDP_UNIFORM_I(k * B.pmax * 4) * kSt);
+    else return sp.planes + rowU(k) * (B.pmax * 4);
+  }
+  DDP_DEV int npU(int k) const { return kTrajBase ? sp.n_planes[(unsigned)DDP_UNIFORM_I(k)] : sp.n_planes[rowU(k)]; }
+  DDP_DEV GSt* KUpU(int k) const {
+    if constexpr (kTrajBase) return at_byte(sp.KU, (unsigned)DDP_UNIFORM_I(k * 100) * kSt);
+    else return sp.KU + rowU(k) * 100;
+  }
   // Knot-record access.  With float storage every entry is an unevaluated hi + lo pair (words a and 19 + a), see
   // x_stride().  pair_round() is the value such a pair holds: what "rounded to the storage type" means for the iterate.
   template <typename Ptr>
@@ -924,11 +965,14 @@ struct Wave {
     (void)buf;
 
     GCSt* rec = XpU(0, k);
-    p.zh = rec[lane < 19 ? lane : 18];
-    p.zl = (sizeof(St) < sizeof(double)) ? rec[19 + (lane < 19 ? lane : 18)] : (St)0;  // see ldx()
+    // (or the two loads' shared lane offset is added to the base first, as a 64-bit vector add, and the knot's after it)
+    if constexpr (kTrajBase) DDP_OPAQUE_S(rec);
+    const int zi = lane < 19 ? lane : 18;
+    p.zh = el(rec, zi);
+    p.zl = (sizeof(St) < sizeof(double)) ? el(rec, 19 + zi) : (St)0;  // see ldx()
     GCSt* pk = planesU(k);
     const int pend = 4 * P - 1;
-    for (int i = 0; i < kNPL; i++) p.pl[i] = pk[lane + 64 * i < pend ? lane + 64 * i : pend];
+    for (int i = 0; i < kNPL; i++) p.pl[i] = el(pk, lane + 64 * i < pend ? lane + 64 * i : pend);
     GCSt* sk = SpU(sp.S[0], k);
     GCSt* yk = SpU(sp.Y[0], k);
     for (int i = 0; i < RPL; i++) {
@@ -938,13 +982,13 @@ struct Wave {
       if (!slot_on(i, P)) continue;
       const int r = (pkv[i] & kRMask) - 1;
       const int rc = r >= 0 ? r : 0;  // rows that do not exist read row 0; their results are masked
-      p.s[i] = sk[rc];
-      if (infeas) p.y[i] = yk[rc];
+      p.s[i] = el(sk, rc);
+      if (infeas) p.y[i] = el(yk, rc);
     }
     if (fwd) {
       GCSt* ku = KUpU(k);
-      p.ku[0] = ku[lane];
-      p.ku[1] = ku[lane + 64 < 100 ? lane + 64 : 99];
+      p.ku[0] = el(ku, lane);
+      p.ku[1] = el(ku, lane + 64 < 100 ? lane + 64 : 99);
     }
   }
   DDP_DEV void commit(const Pre& p, int lane, int P, bool fwd) {
@@ -3409,14 +3453,14 @@ struct Wave {
                   LV(plog)[t].mul(in ? ynew : (Real)1);
                   LV(serr)[t] += in ? fabs(cn + ynew) : (Real)0;
                   if (in) {
-                    yn[r] = (St)ynew;
-                    sn[r] = (St)snew;
+                    el(yn, r) = (St)ynew;
+                    el(sn, r) = (St)snew;
                   }
                 } else {  // DDP:694-703
                   snew = (Real)(St)fma(s, fma(-w1[i], az, oma[t]), -(amu[t] * w1[i]));
                   LV(bad)[t] |= (int)(in & ((cn > bc[i]) | (snew < bs[i])));
                   LV(plog)[t].mul(in ? -cn : (Real)1);
-                  if (in) sn[r] = (St)snew;
+                  if (in) el(sn, r) = (St)snew;
                 }
                 LV(nviol)[t] += (int)(in & (cn >= (Real)2.0e-4));
               }
@@ -3459,14 +3503,14 @@ struct Wave {
                   LV(plog)[t].mul(in ? ynew : (Real)1);
                   LV(serr)[t] += in ? fabs(cn + ynew) : (Real)0;
                   if (in) {
-                    yn[r] = (St)ynew;
-                    sn[r] = (St)snew;
+                    el(yn, r) = (St)ynew;
+                    el(sn, r) = (St)snew;
                   }
                 } else {  // DDP:694-703
                   snew = (Real)(St)fma(s, fma(-w1, az, oma[t]), -(amu[t] * w1));
                   LV(bad)[t] |= (int)(in & ((cn > bc) | (snew < bs)));
                   LV(plog)[t].mul(in ? -cn : (Real)1);
-                  if (in) sn[r] = (St)snew;
+                  if (in) el(sn, r) = (St)snew;
                 }
                 LV(nviol)[t] += (int)(in & (cn >= (Real)2.0e-4));
               }

@@ -1058,6 +1058,10 @@ direct_status_t direct_ddp_create(const direct_ddp_config_t* cfg, direct_ddp_han
   if (cfg->dtype != DIRECT_F32 && cfg->dtype != DIRECT_F64) return fail(DIRECT_ERR_INVALID, "bad dtype");
   if (cfg->max_batch <= 0 || cfg->n_seg_max <= 0 || cfg->p_max <= 0) return fail(DIRECT_ERR_INVALID, "bad sizes");
   if (cfg->p_max > DIRECT_P_LIMIT) return fail(DIRECT_ERR_UNSUPPORTED, "p_max > DIRECT_P_LIMIT");
+  // with float storage the sweeps address a knot by a 32-bit byte offset from its trajectory's first record (Wave::SpU and its kin):
+  // the widest rows of a knot are the 6 p_max + 55 slack rows (padded to a multiple of four) or the 100 of KU
+  if (cfg->dtype == DIRECT_F32 && ((size_t)cfg->n_seg_max + 1) * (size_t)std::max(6 * cfg->p_max + 58, 100) * 4 >= ((size_t)1 << 32))
+    return fail(DIRECT_ERR_UNSUPPORTED, "n_seg_max: a trajectory's rows exceed 4 GiB");
 #if defined(DDP_DEV_RPL2)  // development builds carry the two-slot kernels only: (2 * 64 - 55) / 6 planes
   if (cfg->p_max > 12) return fail(DIRECT_ERR_UNSUPPORTED, "development build (DDP_DEV_RPL2): p_max > 12");
 #endif
