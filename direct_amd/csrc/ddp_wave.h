@@ -177,6 +177,20 @@ extern "C" void ddp_emu_ld2(const void*, int);
 #define DDP_MARK(name)
 #endif
 #endif
+// Price probes of the scalar instruction stream (development builds only): -DDDP_PROBE_SALU_F=K /
+// -DDDP_PROBE_SALU_B=K add K dead `s_nop 0` to every forward round-knot / backward knot.  Results are untouched.
+#define DDP_PROBE_STR2(x) #x
+#define DDP_PROBE_STR(x) DDP_PROBE_STR2(x)
+#if defined(DDP_PROBE_SALU_F) && !defined(DIRECT_EMULATE)
+#define DDP_PROBE_F() asm volatile(".rept " DDP_PROBE_STR(DDP_PROBE_SALU_F) "\n s_nop 0\n .endr")
+#else
+#define DDP_PROBE_F() ((void)0)
+#endif
+#if defined(DDP_PROBE_SALU_B) && !defined(DIRECT_EMULATE)
+#define DDP_PROBE_B() asm volatile(".rept " DDP_PROBE_STR(DDP_PROBE_SALU_B) "\n s_nop 0\n .endr")
+#else
+#define DDP_PROBE_B() ((void)0)
+#endif
 
 namespace direct {
 
@@ -1908,6 +1922,7 @@ struct Wave {
       WSYNC();
       if constexpr (kF) {
         DDP_MARK("B_T2");
+        DDP_PROBE_B();
         // ---- T2: control values and their d/dT, fT, Ru / R'u / R''u (all lanes run all roles, clamped)
         const Real T2 = DDP_UNIFORM_R(T * T), T4 = DDP_UNIFORM_R(T2 * T2);
         Real pw[6];  // T^j as wave-uniform operands
@@ -1978,42 +1993,49 @@ struct Wave {
             ov1[i] = row_ops(L.val, LV(pkc)[i]);
           }
           DDP_LOADS_ISSUED();
+          // one branch on the sweep's mode, the row loop of either mode as its body (see phase R of run_round)
+          const int infeas_rt = infeas;
+          auto rows = [&](auto INFC) {
+            constexpr bool infeas = (int)INFC != 0;
 #pragma unroll
-          for (int i = 0; i < RPL; i++) {
-            if (!slot_on(i, P)) continue;
-            // every lane runs the row arithmetic (empty slots alias row 0); only the stores and the
-            // running maxima are masked
-            const RowK<Real>& rk = rk1[i];
-            const int r = rk.r;
-            const bool in = r >= 0;
-            Real c = row_dot(rk, ov1[i]) + rk.o - (Real)B.k.shift, s = LV(rs)[i], y = LV(ry)[i];
-            Real D, g, rv, frcp_reuse = (Real)0;
-            if (infeas) {  // DDP:535-539, 554
-              Real rm = s * y - mu;
-              rv = s * (c + y) - rm;  // rhat
-              Real yinv = frcp(y);
-              D = s * yinv;
-              g = s + yinv * rv;
-              LV(C.e_mu) = fmax(LV(C.e_mu), in ? fmax(fabs(rm), fabs(c + y)) : (Real)0);
-            } else {  // DDP:583-587, 601
-              rv = s * c + mu;
-              Real cinv = frcp(c);
-              frcp_reuse = cinv;
-              D = s * cinv;
-              g = -mu * cinv;  // s - r/c
-              LV(C.e_mu) = fmax(LV(C.e_mu), in ? fabs(rv) : (Real)0);
+            for (int i = 0; i < RPL; i++) {
+              if (!slot_on(i, P)) continue;
+              // every lane runs the row arithmetic (empty slots alias row 0); only the stores and the
+              // running maxima are masked
+              const RowK<Real>& rk = rk1[i];
+              const int r = rk.r;
+              const bool in = r >= 0;
+              Real c = row_dot(rk, ov1[i]) + rk.o - (Real)B.k.shift, s = LV(rs)[i], y = LV(ry)[i];
+              Real D, g, rv, frcp_reuse = (Real)0;
+              if (infeas) {  // DDP:535-539, 554
+                Real rm = s * y - mu;
+                rv = s * (c + y) - rm;  // rhat
+                Real yinv = frcp(y);
+                D = s * yinv;
+                g = s + yinv * rv;
+                LV(C.e_mu) = fmax(LV(C.e_mu), in ? fmax(fabs(rm), fabs(c + y)) : (Real)0);
+              } else {  // DDP:583-587, 601
+                rv = s * c + mu;
+                Real cinv = frcp(c);
+                frcp_reuse = cinv;
+                D = s * cinv;
+                g = -mu * cinv;  // s - r/c
+                LV(C.e_mu) = fmax(LV(C.e_mu), in ? fabs(rv) : (Real)0);
+              }
+              if constexpr (kGains) {
+                // for phase R2: infeasible mode needs c and rhat; feasible mode only the two quotients r / c and s / c, so
+                // that the slack gain ks = -(r + s cu ku) / c costs no second reciprocal there
+                LV(rc)[i] = infeas ? c : D;
+                LV(rr)[i] = infeas ? rv : rv * frcp_reuse;
+              }
+              if (in) {
+                L.drow[r] = (Acc)D;
+                L.grow[r] = (Acc)g;
+              }
             }
-            if constexpr (kGains) {
-              // for phase R2: infeasible mode needs c and rhat; feasible mode only the two quotients r / c and s / c, so
-              // that the slack gain ks = -(r + s cu ku) / c costs no second reciprocal there
-              LV(rc)[i] = infeas ? c : D;
-              LV(rr)[i] = infeas ? rv : rv * frcp_reuse;
-            }
-            if (in) {
-              L.drow[r] = (Acc)D;
-              L.grow[r] = (Acc)g;
-            }
-          }
+          };
+          if (infeas_rt) rows(IC<1>{});
+          else rows(IC<0>{});
         } else {
           // (back) the role descriptors of phase H, a phase ahead as in the fused knot's phase S2
           LV(tw_h0) = L.lt[0][lane];
@@ -2755,7 +2777,8 @@ struct Wave {
     int ok = 1, kfail = 0;
     int ks = -1;  // knots ks .. 0 are the helpers': through records
     // (one instantiation for both modes: per-mode copies of the fused loop measured no faster, and the compiler contracts
-    // the infeasible rows' arithmetic differently in a copy of its own - the bits would depend on who ran the knot)
+    // the infeasible rows' arithmetic differently in a copy of its own - the bits would depend on who ran the knot.
+    // Phase R1 alone does branch on the mode once, bwd_knot: every knot runner shares that one copy per mode)
     ok = bwd_fused_run<kGains, -1>(C, bs, pend, kfloor, ks, kfail);
 #if defined(DDP_TIMELINE) && !defined(DIRECT_EMULATE)
     tl_split_ += ks + 1;
@@ -2988,6 +3011,9 @@ struct Wave {
     set_sweep_ptrs(cur, trial_buf(cur, step0), trial_buf(cur, step0 + NT - 1));
     Real alpha[NT], oma[NT], amu[NT];  // step size, 1 - alpha (exact: alpha = 2^-step), alpha * mu
     TrialRes* tr = res;
+    // Inside the knot loop: is trial t still running?  A single-trial round leaves the loop at the knot where its trial
+    // ends, so there it is by construction - the phases of that round carry no test of it.
+    auto live = [&](int t) { return NT == 1 || tr[t].alive != 0; };
 #pragma unroll
     for (int t = 0; t < NT; t++) {
       tr[t].alive = 1;
@@ -3074,6 +3100,7 @@ struct Wave {
       }
       WSYNC();
     DDP_MARK("F_D");
+      DDP_PROBE_F();
       // ---- D: dx, du = alpha ku + Ku dx, u+ = u + du (DDP:689 / 695); powers of the new T
       const Real To2 = DDP_UNIFORM_R(To * To), To4 = DDP_UNIFORM_R(To2 * To2);
       Real pwo[6];  // T^j, j = 0..5, of the old iterate as wave-uniform operands (same values as the tables)
@@ -3159,7 +3186,7 @@ struct Wave {
 #pragma unroll
         for (int t = 0; t < NT; t++) {
           Tn[t] = (Real)0;
-          if (tr[t].alive) {
+          if (live(t)) {
             typename Lds::FwdT& F = L.ft[t];
             PLV(Real, unew);
             PLV(Real, dxl);
@@ -3309,7 +3336,7 @@ struct Wave {
       } else {
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-          if (tr[t].alive) {
+          if (live(t)) {
             typename Lds::FwdT& F = L.ft[t];
             LANES {
               {  // lanes 0..44: control values; 45..53: x+ (rows of [F|G]); 54..62: jerk-cost products (rows of R)
@@ -3374,7 +3401,7 @@ struct Wave {
       WSYNC();
 #pragma unroll
       for (int t = 0; t < NT; t++)
-        if (tr[t].alive) tr[t].qsum += knot_cost(Tn[t], L.ft[t].qp);
+        if (live(t)) tr[t].qsum += knot_cost(Tn[t], L.ft[t].qp);
     DDP_MARK("F_R");
       // ---- R: rows: s+, y+, c+, fraction-to-boundary tests
       // The reference steps the slacks and duals with gains it has formed in the backward pass (DDP:565-575, 610-614,
@@ -3404,68 +3431,76 @@ struct Wave {
             oo[i] = row_ops(L.val, LV(pkc)[i]);
           }
           DDP_LOADS_ISSUED();
-          // what belongs to the old iterate is shared by the trials of the round
-          Real co[RPL], w1[RPL], w2[RPL], bs[RPL], bc[RPL];
+          // The mode is wave-uniform and fixed for the sweep: ONE branch on it, with the row loops of either mode as its
+          // bodies (tested inside them it costs a scalar compare-and-branch chain per row slot and use).  Each body holds
+          // the operations of its mode in the order they always had.
+          auto rows = [&](auto INFC) {
+            constexpr bool infeas = (int)INFC != 0;
+            // what belongs to the old iterate is shared by the trials of the round
+            Real co[RPL], w1[RPL], w2[RPL], bs[RPL], bc[RPL];
 #pragma unroll
-          for (int i = 0; i < RPL; i++) {
-            const Real s = LV(rs)[i];
-            co[i] = row_dot(rks_[i], oo[i]) + rks_[i].o - (Real)B.k.shift;
-            bs[i] = omt * s;
-            if (infeas) {
-              const Real y = LV(ry)[i];
-              w1[i] = frcp(y);
-              w2[i] = s * (co[i] + y) - (s * y - mu);  // rhat (DDP:536-537)
-              bc[i] = omt * y;
-            } else {
-              w1[i] = frcp(co[i]);
-              w2[i] = mu * w1[i];
-              bc[i] = omt * co[i];
-            }
-          }
-#pragma unroll
-          for (int t = 0; t < NT; t++) {
-            if (tr[t].alive) {
-              GSt* sn = SpU(sp.S[1 + t], k);
-              Row3 og[RPL], ov[RPL];  // one trial's operands at a time: both trials' would not fit the register file
-#pragma unroll
-              for (int i = 0; i < RPL; i++) {
-                og[i] = row_ops(L.ft[t].G, LV(pkc)[i]);
-                ov[i] = row_ops(L.ft[t].valn, LV(pkc)[i]);
+            for (int i = 0; i < RPL; i++) {
+              const Real s = LV(rs)[i];
+              co[i] = row_dot(rks_[i], oo[i]) + rks_[i].o - (Real)B.k.shift;
+              bs[i] = omt * s;
+              if (infeas) {
+                const Real y = LV(ry)[i];
+                w1[i] = frcp(y);
+                w2[i] = s * (co[i] + y) - (s * y - mu);  // rhat (DDP:536-537)
+                bc[i] = omt * y;
+              } else {
+                w1[i] = frcp(co[i]);
+                w2[i] = mu * w1[i];
+                bc[i] = omt * co[i];
               }
-              DDP_LOADS_ISSUED();
+            }
 #pragma unroll
-              for (int i = 0; i < RPL; i++) {
-                // branch-free rows: empty slots alias row 0, their stores / reductions are masked
-                const RowK<Real>& rk = rks_[i];
-                const int r = rk.r;
-                const bool in = r >= 0;
-                const Real s = LV(rs)[i];
-                const Real az = row_dot(rk, og[i]);
-                const Real cn = row_dot(rk, ov[i]) + rk.o - (Real)B.k.shift;
-                Real snew;
-                if (infeas) {  // DDP:680-687
-                  GSt* yn = SpU(sp.Y[1 + t], k);
-                  const Real y = LV(ry)[i];
-                  const Real ynew = (Real)(St)(fma(-alpha[t], co[i] + y, y) - az);
-                  snew = (Real)(St)fma(w1[i], fma(alpha[t], w2[i], s * az), s);
-                  // bitwise, not short-circuit: the latter compiles to nested exec-masked branches per row
-                  LV(bad)[t] |= (int)(in & ((ynew < bc[i]) | (snew < bs[i])));
-                  LV(plog)[t].mul(in ? ynew : (Real)1);
-                  LV(serr)[t] += in ? fabs(cn + ynew) : (Real)0;
-                  if (in) {
-                    el(yn, r) = (St)ynew;
-                    el(sn, r) = (St)snew;
-                  }
-                } else {  // DDP:694-703
-                  snew = (Real)(St)fma(s, fma(-w1[i], az, oma[t]), -(amu[t] * w1[i]));
-                  LV(bad)[t] |= (int)(in & ((cn > bc[i]) | (snew < bs[i])));
-                  LV(plog)[t].mul(in ? -cn : (Real)1);
-                  if (in) el(sn, r) = (St)snew;
+            for (int t = 0; t < NT; t++) {
+              if (live(t)) {
+                GSt* sn = SpU(sp.S[1 + t], k);
+                Row3 og[RPL], ov[RPL];  // one trial's operands at a time: both trials' would not fit the register file
+#pragma unroll
+                for (int i = 0; i < RPL; i++) {
+                  og[i] = row_ops(L.ft[t].G, LV(pkc)[i]);
+                  ov[i] = row_ops(L.ft[t].valn, LV(pkc)[i]);
                 }
-                LV(nviol)[t] += (int)(in & (cn >= (Real)2.0e-4));
+                DDP_LOADS_ISSUED();
+#pragma unroll
+                for (int i = 0; i < RPL; i++) {
+                  // branch-free rows: empty slots alias row 0, their stores / reductions are masked
+                  const RowK<Real>& rk = rks_[i];
+                  const int r = rk.r;
+                  const bool in = r >= 0;
+                  const Real s = LV(rs)[i];
+                  const Real az = row_dot(rk, og[i]);
+                  const Real cn = row_dot(rk, ov[i]) + rk.o - (Real)B.k.shift;
+                  Real snew;
+                  if (infeas) {  // DDP:680-687
+                    GSt* yn = SpU(sp.Y[1 + t], k);
+                    const Real y = LV(ry)[i];
+                    const Real ynew = (Real)(St)(fma(-alpha[t], co[i] + y, y) - az);
+                    snew = (Real)(St)fma(w1[i], fma(alpha[t], w2[i], s * az), s);
+                    // bitwise, not short-circuit: the latter compiles to nested exec-masked branches per row
+                    LV(bad)[t] |= (int)(in & ((ynew < bc[i]) | (snew < bs[i])));
+                    LV(plog)[t].mul(in ? ynew : (Real)1);
+                    LV(serr)[t] += in ? fabs(cn + ynew) : (Real)0;
+                    if (in) {
+                      el(yn, r) = (St)ynew;
+                      el(sn, r) = (St)snew;
+                    }
+                  } else {  // DDP:694-703
+                    snew = (Real)(St)fma(s, fma(-w1[i], az, oma[t]), -(amu[t] * w1[i]));
+                    LV(bad)[t] |= (int)(in & ((cn > bc[i]) | (snew < bs[i])));
+                    LV(plog)[t].mul(in ? -cn : (Real)1);
+                    if (in) el(sn, r) = (St)snew;
+                  }
+                  LV(nviol)[t] += (int)(in & (cn >= (Real)2.0e-4));
+                }
               }
             }
-          }
+          };
+          if (infeas) rows(IC<1>{});
+          else rows(IC<0>{});
         } else {  // double storage / many row slots: row by row, both trials of a row together (the registers hold no more)
           for (int i = 0; i < RPL; i++) {
             if (!slot_on(i, P)) continue;
@@ -3488,7 +3523,7 @@ struct Wave {
             }
 #pragma unroll
             for (int t = 0; t < NT; t++) {
-              if (tr[t].alive) {
+              if (live(t)) {
                 typename Lds::FwdT& F = L.ft[t];
                 GSt* sn = SpU(sp.S[1 + t], k);
                 const Real az = row_lin(F.G, rk);
@@ -3519,7 +3554,7 @@ struct Wave {
         }
 #pragma unroll
         for (int t = 0; t < NT; t++) {
-          if (tr[t].alive) {
+          if (live(t)) {
             LV(plog)[t].norm();
             if (lane < 19) stx(XpU(1 + t, k), lane, L.ft[t].zn[lane]);
             if (lane < 9) L.ft[t].xn[lane] = L.ft[t].xnx[lane];

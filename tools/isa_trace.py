@@ -6,7 +6,8 @@ following fall-through at every s_cbranch_exec* (a lane-mask skip: the block run
 uniform branches (scc / vcc), the direction given on the command line: LABEL = always taken, LABEL@N = taken at its Nth
 encounter only (loop exits), every other conditional branch falls through.  Backward branches are loops: taken `TRIPS - 1` times (--p, default 3: the
 plane loop of phase S for P = 6 at unroll 2).  Prints the uniform branches it met (so that the policy can be reviewed)
-and VALU / SALU / LDS / VMEM counts per phase."""
+and VALU / SALU / LDS / VMEM counts per phase, the SALU count split into s_waitcnt / s_nop / the exec-mask and branch
+skeleton (saveexec, 64-bit mask logic and moves, s_cselect_b64, branches) / the rest (address and loop arithmetic)."""
 import re
 import sys
 
@@ -22,6 +23,7 @@ trips = int(opts.get("p", 3))
 txt = open(path).read()
 m = re.search(r"^%s\w*:.*?\.Lfunc_end\d+:" % kern, txt, re.S | re.M)
 lines = m.group(0).split("\n")
+SKELETON = re.compile(r"s_(and|andn2|or|orn2|xor)_saveexec_b64|s_(and|andn2|or|orn2|xor|mov|cselect)_b64|s_cbranch_\w+|s_branch")
 label_at = {}
 for i, l in enumerate(lines):
     mm = re.match(r"^(\.LBB\d+_\d+):", l)
@@ -48,7 +50,7 @@ while pc < len(lines) and steps < 200000:
         pc += 1
         continue
     op, rest = t.group(1), t.group(2)
-    d = stats.setdefault(phase, dict(v=0, s=0, ds=0, gl=0, f64=0, cvt=0, rl=0, mov=0, cnd=0, i32=0))
+    d = stats.setdefault(phase, dict(v=0, s=0, ds=0, gl=0, f64=0, cvt=0, rl=0, mov=0, cnd=0, i32=0, sw=0, sn=0, sk=0, sa=0))
     if phase not in order:
         order.append(phase)
     if op.startswith("v_"):
@@ -67,6 +69,14 @@ while pc < len(lines) and steps < 200000:
             d["i32"] += 1
     elif op.startswith("s_"):
         d["s"] += 1
+        if op == "s_waitcnt":
+            d["sw"] += 1
+        elif op == "s_nop":
+            d["sn"] += 1
+        elif SKELETON.match(op):
+            d["sk"] += 1
+        else:
+            d["sa"] += 1
     elif op.startswith("ds_"):
         d["ds"] += 1
     elif op.startswith(("global_", "buffer_", "flat_", "scratch_")):
@@ -102,12 +112,14 @@ print("uniform branches met (phase, op, target, taken):")
 import collections
 for x, c in collections.Counter(met).items():
     print("  ", x, "x%d" % c)
-print("%-8s %5s %5s %5s %4s | %5s %4s %5s %4s %4s %4s" % ("phase", "VALU", "SALU", "LDS", "VMEM", "f64", "cvt", "lane", "mov", "cnd", "i32"))
-tot = dict(v=0, s=0, ds=0, gl=0, f64=0, cvt=0, rl=0, mov=0, cnd=0, i32=0)
+FMT = "%-8s %5s %5s %5s %4s | %5s %4s %5s %4s %4s %4s | %5s %4s %5s %5s"
+print(FMT % ("phase", "VALU", "SALU", "LDS", "VMEM", "f64", "cvt", "lane", "mov", "cnd", "i32", "swait", "snop", "sskel", "sarit"))
+FMT = FMT.replace("s", "d").replace("%-8d", "%-8s")
+tot = dict(v=0, s=0, ds=0, gl=0, f64=0, cvt=0, rl=0, mov=0, cnd=0, i32=0, sw=0, sn=0, sk=0, sa=0)
 for k in order:
     d = stats[k]
     for q in tot:
         tot[q] += d[q]
-    print("%-8s %5d %5d %5d %4d | %5d %4d %5d %4d %4d %4d" % (k, d["v"], d["s"], d["ds"], d["gl"], d["f64"], d["cvt"], d["rl"], d["mov"], d["cnd"], d["i32"]))
+    print(FMT % (k, d["v"], d["s"], d["ds"], d["gl"], d["f64"], d["cvt"], d["rl"], d["mov"], d["cnd"], d["i32"], d["sw"], d["sn"], d["sk"], d["sa"]))
 d = tot
-print("%-8s %5d %5d %5d %4d | %5d %4d %5d %4d %4d %4d" % ("TOTAL", d["v"], d["s"], d["ds"], d["gl"], d["f64"], d["cvt"], d["rl"], d["mov"], d["cnd"], d["i32"]))
+print(FMT % ("TOTAL", d["v"], d["s"], d["ds"], d["gl"], d["f64"], d["cvt"], d["rl"], d["mov"], d["cnd"], d["i32"], d["sw"], d["sn"], d["sk"], d["sa"]))
