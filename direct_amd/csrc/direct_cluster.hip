@@ -38,8 +38,10 @@
 #include "grid_path_math.h"
 #include "host_stage.h"
 #include "hull_core.h"
+#include "resident_state.h"
 
 namespace {
+namespace rs = ::direct::resident;
 
 constexpr uint8_t F_USE = 1, F_INVALID = 2, F_INSIDE = 4, F_OBS = 8;
 constexpr int KEY_NONE = 0x7f7f7f7f;
@@ -1018,14 +1020,13 @@ struct direct_cluster_handle_s {
   uint8_t* inside_tmp = nullptr;
   int* seeds = nullptr;
   int32_t *st_vertex = nullptr, *st_xyz = nullptr, *st_num = nullptr, *st_iters = nullptr, *st_rtn = nullptr;  // device staging of host outputs
-  bool have_map = false;
   hipStream_t stream = nullptr;
   hs::EventPair ev;  // direct_cluster_last_ms
   std::vector<void*> allocs;
   HullDev H = {};          // scratch of hull_planes_batch, allocated by its first call
   bool have_hull = false;
   int convex_grid = 2048;    // workgroups per seed of k_convex (DIRECT_CLUSTER_CONVEX_GRID: experiments)
-  int resident_batch = 0;    // seeds of the last polygon_generation_batch whose clusters are still in D.cluster / D.el (0: none)
+  rs::State rs = {};         // what of all this is resident and still describes the map: the one owner (resident_state.h)
   hs::Block hull_out;        // device staging of its host outputs
   PathDev P = {};            // workspace of grid_path_batch, allocated by its first call (never shrunk, freed in destroy)
   bool have_path = false;
@@ -1036,8 +1037,6 @@ struct direct_cluster_handle_s {
   hs::Block plan_io;  // device staging of its host arrays, grown on demand
   int32_t* dist[2] = {nullptr, nullptr};  // the distance field (in dist[0]) and its ping-pong partner, allocated by the first distance_field
   unsigned long long* dist_cnt = nullptr;  // [2] the counters behind its stats
-  bool dist_valid = false;  // dist[0] describes the map the handle holds
-  int32_t dist_cap2 = 0;    // the cap2 the field in dist[0] was built with (DIRECT_DIST_NONE: uncapped): grid_path_clear_batch's cap rule
   double* path_pen = nullptr;  // [gp::kMaxPenalty] the penalty table of grid_path_clear_batch, allocated by its first call with a table
   hs::Block clear_ws;  // workspace of plan_clearance_batch (start times, per-slot minima), grown on demand
   hs::Block clear_io;  // device staging of its host arrays, grown on demand
@@ -1046,20 +1045,14 @@ struct direct_cluster_handle_s {
   hs::Block fan_ws;    // workspace of grid_path_fan_batch (goals, their grouping, bounds, one read-back ring or two per goal), grown on demand
   hs::Block fan_out;   // device staging of its host outputs, grown on demand
   int fan_bound_every = 1;  // rounds between two k_fan_bound launches: 1 or 8 (DIRECT_CLUSTER_FAN_BOUND_EVERY: experiments)
-  unsigned long long dist_serial = 0;  // successful direct_cluster_distance_field calls: the key of the floor tables below
   int* floor_tab[cc::kFloorSlots] = {};        // floor tables of cube_corridor_clear_batch (layout of D.sat), allocated by its first clear-mode call
-  cc::FloorSlot floor_slot[cc::kFloorSlots] = {};  // what each holds
-  unsigned long long floor_clock = 0;  // ticks at every use of a slot: least recently used is the smallest FloorSlot::used
   int32_t *comp_label = nullptr, *comp_size = nullptr;  // labels and sizes of free_components, allocated by its first call
   unsigned long long* comp_cnt = nullptr;  // [4] the counters behind its stats and its error word
-  fc::Key comp_key = {};                   // what the resident labels were built from (valid == 0: none)
-  unsigned long long map_gen = 0, field_gen = 0;  // calls that set the map / built a field so far: the labels' staleness key
   hs::Block reach_in, reach_out;  // device staging of reachable_batch's host inputs / host outputs, grown on demand
   hs::Block corr_ws;   // workspace of corridor_batch (walk states, plane stacks, owner table, seed list, a chunk's hull outputs), grown on demand
   hs::Block corr_in, corr_out;  // device staging of its host inputs / host outputs, grown on demand
   uint8_t* scan_raw = nullptr;            // the scan grid of map_integrate_scan (the map's size and layout), allocated by its first call
   unsigned long long* scan_cnt = nullptr; // [kScanCounters] its counters
-  bool have_scan = false;                 // scan_raw holds what the scans so far left
   hs::Block scan_ws;                      // the two intermediate grids of its inflation, grown by the first call that inflates in y or z
   bool scan_test_store = true;            // the carve loads a byte before it stores (DIRECT_CLUSTER_SCAN_STORE=plain: experiments)
   bool scan_timing = false;               // record the phases' events (DIRECT_CLUSTER_SCAN_TIMING=1: tools/map_scan_bench.py)
@@ -1122,7 +1115,8 @@ hipError_t path_rounds(direct_cluster_handle_t h, size_t n_slots, long long lim,
 }
 
 // The clearance parameters of grid_path_clear_batch and grid_path_fan_batch, in two steps, because what the arguments alone
-// decide is refused before what the handle holds: each gives the refusal's text, or null.
+// decide is refused before what the handle holds: each gives the refusal's text, or null.  This is the first; the second is
+// rs::State::field_refusal.
 const char* clear_args_refusal(int32_t min_d2, int32_t n_penalty, const double* penalty) {
   if (min_d2 < 0) return "min_d2 must not be negative";
   if (n_penalty < 0 || n_penalty > gp::kMaxPenalty) return "n_penalty outside [0, 65536]";
@@ -1131,13 +1125,10 @@ const char* clear_args_refusal(int32_t min_d2, int32_t n_penalty, const double* 
     if (!std::isfinite(penalty[i]) || !(penalty[i] >= 0.0)) return "penalty entries must be finite and not negative";
   return nullptr;
 }
-const char* clear_field_refusal(direct_cluster_handle_t h, int32_t min_d2, int32_t n_penalty) {
-  if (!h->dist_valid) return "no valid distance field: call direct_cluster_distance_field after the map changes";
-  // a stored cap2 means "at least cap2": neither the floor nor the table may tell values at or above it apart (an uncapped
-  // field has cap2 = DIRECT_DIST_NONE, which refuses nothing)
-  if (min_d2 > h->dist_cap2 || n_penalty > h->dist_cap2) return "min_d2 or n_penalty above the cap2 the distance field was built with";
-  return nullptr;
-}
+
+// a memory kind of the C-ABI, and what every call says to anything else
+const char* const kMemRefusal = "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE";
+bool mem_kind(int32_t mem) { return mem == DIRECT_MEM_HOST || mem == DIRECT_MEM_DEVICE; }
 
 // The penalty table on the device: path_pen, allocated by the first call with a table, and the upload of this call's entries
 direct_status_t upload_penalty(direct_cluster_handle_t h, int32_t n_penalty, const double* penalty, const char* who) {
@@ -1157,7 +1148,7 @@ const char* plan_rows_refusal(direct_cluster_handle_t h, const In* in, const Out
   if (!h || !in || !out || !in->n_seg || !in->T || !out->status) return "null argument";
   if (in->batch <= 0 || in->n_seg_max <= 0) return "batch and n_seg_max must be positive";
   if ((in->bez != nullptr) == (in->poly != nullptr)) return "exactly one of bez and poly";
-  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE";
+  if (!mem_kind(in->mem)) return kMemRefusal;
   if (in->dtype != DIRECT_F32 && in->dtype != DIRECT_F64) return "dtype is neither DIRECT_F32 nor DIRECT_F64";
   if (in->depth < 0 || in->depth > pk::kMaxDepth) return "depth outside [0, 12]";
   return nullptr;
@@ -1168,7 +1159,7 @@ const char* plan_map_refusal(direct_cluster_handle_t h, const In* in, double ext
   if (!std::isfinite(extent) || !(extent >= 0.0)) return extent_refusal;
   for (int a = 0; a < 3; a++)
     if (!std::isfinite(in->map_lower[a])) return "map_lower must be finite";
-  return h->have_map ? nullptr : "the handle has no map";
+  return h->rs.has_map() ? nullptr : "the handle has no map";
 }
 // Their last refusal, then the row view (without S), the grid fields both Grids have and the four inputs on the call's Stage
 template <class In, class Grid>
@@ -1226,6 +1217,93 @@ hipError_t download_fields(direct_cluster_handle_t h, double* dist, size_t n, in
                         mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream);
 }
 
+// grid_path_batch, grid_path_clear_batch and grid_path_fan_batch behind their refusals: what one call is ...
+struct PathCall {
+  const char* who;                 // opens its messages
+  int n_field, n_path;             // fields relaxed (at most max_batch), paths read back from them
+  int32_t path_capacity, max_rounds, mem;
+  const int32_t *starts, *goals;   // [n_field][3] each: every field's (start, goal); the fan passes its sources for both
+  bool clear;                      // reads the distance field under (min_d2, the n_penalty entries of penalty)
+  int32_t min_d2, n_penalty;
+  const double* penalty;
+  double* dist;                    // the caller's array for the fields, or null
+};
+// ... and what all three do.  stage(P, C) registers what is left to register and uploads the call's blocks (its refusal ends the
+// call), relax(P, C, r) launches round r, trace(P, C, done) the read-back; `out` is the Stage whose outputs go back.
+template <class StageFn, class Relax, class Trace>
+direct_status_t grid_path_run(direct_cluster_handle_t h, const PathCall& c, const hs::Stage& out, StageFn stage, Relax relax, Trace trace) {
+  const std::string who(c.who);
+  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
+    return cfail(DIRECT_ERR_DEVICE, who + ": workspace allocation: " + hipGetErrorString(ae));
+  if (const direct_status_t us = upload_penalty(h, c.n_penalty, c.penalty, c.who); us != DIRECT_OK) return us;
+  PathDev& P = h->P;
+  PathClearDev C = c.clear ? clear_dev(h, c.min_d2, c.n_penalty) : PathClearDev{};
+  if (const direct_status_t rc = stage(P, C)) return rc;
+  P.cap = c.path_capacity;
+  const size_t nf = (size_t)c.n_field;
+  const std::vector<int> ends = pack_ends(nf, c.starts, c.goals);
+  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nf * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), c.n_field), dim3(256), 0, h->stream, P);
+  CHIP_TRY(hipGetLastError());
+  const long long lim = c.max_rounds > 0 ? (long long)c.max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
+  int done = 0;
+  hipError_t e = path_rounds(h, nf, lim, &done, [&](int r) { relax(P, C, r); });
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, who + ": rounds: " + hipGetErrorString(hs::drain(h->stream, e)));
+  trace(P, C, done);
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, download_fields(h, c.dist, nf, c.mem, hs::stage_download(out, h->stream, e)));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, who + ": " + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+// The stage() of grid_path_batch and grid_path_clear_batch, one path per field: ONE block, path_out, for the read-back rings (scratch
+// slices, needed whatever `mem` is; the ring of D2 values in clear mode only) and the staging of host outputs (nothing is filled).
+// user / dev: path_xyz, path_len, path_cost, stats, rtn, path_d2, path_min_d2 - the last two null outside clear mode.
+direct_status_t path_pair_stage(direct_cluster_handle_t h, const PathCall& c, hs::Stage& st, PathDev& P, PathClearDev& C, void* const* user, void** dev) {
+  const size_t nb = (size_t)c.n_path, cap = (size_t)c.path_capacity;
+  const size_t sz[7] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t),
+                        nb * cap * sizeof(int32_t), nb * sizeof(int32_t)};
+  hs::stage_scratch(st, &P.ring, nb * cap * sizeof(int));
+  if (c.clear) hs::stage_scratch(st, &C.ring_d2, nb * cap * sizeof(int));
+  for (int i = 0; i < 7; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
+  CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
+  return DIRECT_OK;
+}
+
+// map_from_cloud and map_integrate_scan: what both refuse of a cloud - the points and their memory kind first in both, the stride
+// and the resolution where each call has them among its own checks ...
+const char* cloud_refusal(int64_t n_points, int32_t mem, const float* xyz) {
+  if (n_points < 0 || (n_points > 0 && !xyz)) return "n_points negative, or points without a pointer";
+  return mem_kind(mem) ? nullptr : kMemRefusal;
+}
+const char* stride_refusal(int32_t stride) { return stride != 3 && stride != 4 ? "stride must be 3 or 4 floats per point" : nullptr; }
+const char* resolution_refusal(double resolution) {
+  return !std::isfinite(resolution) || !(resolution > 0.0) ? "resolution must be finite and positive" : nullptr;
+}
+// ... and the cloud on the device: the caller's own pointer, or a host cloud's copy in cloud_in (enqueued)
+direct_status_t cloud_on_device(direct_cluster_handle_t h, int64_t n_points, int32_t stride, int32_t mem, const float* xyz, const float** dev) {
+  *dev = xyz;
+  if (mem != DIRECT_MEM_HOST || n_points <= 0) return DIRECT_OK;
+  const size_t bytes = (size_t)n_points * stride * sizeof(float);
+  CHIP_TRY(hs::grow(h->cloud_in, h->stream, bytes));
+  CHIP_TRY(hipMemcpyAsync(h->cloud_in.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
+  *dev = (const float*)h->cloud_in.p;
+  return DIRECT_OK;
+}
+
+// The four fetches behind their refusals: one resident array, or two of one size, to the caller in either memory kind (a null
+// destination is skipped), and the drain
+direct_status_t fetch_resident(direct_cluster_handle_t h, int32_t mem, size_t bytes, void* dst, const void* src, void* dst2 = nullptr,
+                               const void* src2 = nullptr) {
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const hipMemcpyKind kind = mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (dst) CHIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, h->stream));
+  if (dst2) CHIP_TRY(hipMemcpyAsync(dst2, src2, bytes, kind, h->stream));
+  CHIP_TRY(hipStreamSynchronize(h->stream));
+  return DIRECT_OK;
+}
+
 // cube_corridor_batch, cube_corridor_clear_batch and corridor_batch, whose structs share these field names.  What all refuse, in
 // the plain call's order; DIRECT_OK: nothing to refuse.
 // `more` is a further refusal that the call's arguments alone decide (or null): it comes before what the handle holds.
@@ -1235,14 +1313,13 @@ direct_status_t cube_corridor_refusal(direct_cluster_handle_t h, const In* in, c
   if (in->batch <= 0 || in->path_capacity <= 0 || in->seg_capacity <= 0 || in->itr_inflate_max <= 0)
     return cfail(DIRECT_ERR_INVALID, "batch, path_capacity, seg_capacity and itr_inflate_max must be positive");
   if (in->p_max < cc::kPlanes) return cfail(DIRECT_ERR_INVALID, "p_max below 6");
-  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
-    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!mem_kind(in->mem_in) || !mem_kind(out->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
   if (in->plane_dtype != DIRECT_F32 && in->plane_dtype != DIRECT_F64) return cfail(DIRECT_ERR_INVALID, "plane_dtype is neither DIRECT_F32 nor DIRECT_F64");
   if (!std::isfinite(in->resolution) || !(in->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
   for (int a = 0; a < 3; a++)
     if (!std::isfinite(in->map_lower[a])) return cfail(DIRECT_ERR_INVALID, "map_lower must be finite");
   if (more) return cfail(DIRECT_ERR_INVALID, more);
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
   const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
   if (slots >= (1ull << 28) || segs * (size_t)in->p_max >= (1ull << 28))
     return cfail(DIRECT_ERR_UNSUPPORTED, "batch * path_capacity or batch * seg_capacity * p_max of 2^28 or more");
@@ -1297,7 +1374,7 @@ direct_status_t cube_corridor_run(direct_cluster_handle_t h, const direct_cube_c
 // The device part of polygon_generation_batch for `batch` <= max_batch seeds in DEVICE memory (seeds[batch][3]): flagClear, the
 // cube, the rounds of polytopeCluster_cpu and the emit into DEVICE outputs (any may be null).  Enqueues on the handle's stream and
 // waits for its own liveness read-backs, the last of which leaves the elements' counters in `el`; events, the copies of host arrays
-// and resident_batch are the caller's.
+// and what the handle's rs hears of the clusters are the caller's.
 direct_status_t generation_run(direct_cluster_handle_t h, int batch, const int* seeds, int itr_inflate_max, int itr_cluster_max, int32_t* dv,
                                int32_t* dc, int32_t* dn, int32_t* di, int32_t* dr, std::vector<Elem>& el) {
   Dev& D = h->D;
@@ -1474,28 +1551,26 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
 
 direct_status_t direct_cluster_set_map(direct_cluster_handle_t h, int32_t mem, const uint8_t* map_data) {
   if (!h || !map_data) return cfail(DIRECT_ERR_INVALID, "null argument");
-  h->dist_valid = false;  // the map is about to change: a distance field no longer describes it
-  h->map_gen++;           // nor do the labels of free_components
+  h->rs.map_edit_began();  // the map is about to change: neither a distance field nor the labels of free_components describe it
   CHIP_TRY(hipSetDevice(h->cfg.device));
   CHIP_TRY(hipMemcpyAsync(h->map, map_data, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
                           h->stream));
   CHIP_TRY(hipStreamSynchronize(h->stream));
   CHIP_TRY(rebuild_sat(h));
   CHIP_TRY(hipStreamSynchronize(h->stream));
-  h->have_map = true;
+  h->rs.map_ready();
   return DIRECT_OK;
 }
 
 direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const direct_map_cloud_t* p, int64_t n_points, int32_t mem,
                                               const float* xyz, int64_t* stats) {
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
-  h->dist_valid = false;  // whether or not the call succeeds: a distance field is rebuilt by its caller
-  h->map_gen++;           // and so are the labels of free_components
-  if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
-  if (!std::isfinite(p->cloud_margin) || !(p->cloud_margin >= 0.0)) return cfail(DIRECT_ERR_INVALID, "cloud_margin must be finite and not negative");
-  if (p->stride != 3 && p->stride != 4) return cfail(DIRECT_ERR_INVALID, "stride must be 3 or 4 floats per point");
+  h->rs.map_edit_began();  // whether or not the call succeeds: a distance field and the labels of free_components are rebuilt by its caller
+  const char* why = cloud_refusal(n_points, mem, xyz);
+  if (!why) why = resolution_refusal(p->resolution);
+  if (!why && (!std::isfinite(p->cloud_margin) || !(p->cloud_margin >= 0.0))) why = "cloud_margin must be finite and not negative";
+  if (!why) why = stride_refusal(p->stride);
+  if (why) return cfail(DIRECT_ERR_INVALID, why);
   if (p->border != DIRECT_MAP_BORDER_CLAMP && p->border != DIRECT_MAP_BORDER_DROP) return cfail(DIRECT_ERR_INVALID, "unknown border convention");
   if (p->mode != DIRECT_MAP_REPLACE && p->mode != DIRECT_MAP_ADD) return cfail(DIRECT_ERR_INVALID, "unknown mode");
   for (int a = 0; a < 3; a++)
@@ -1513,17 +1588,10 @@ direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const d
   C.border = p->border; C.stride = p->stride; C.n = n_points; C.map = h->map;
   if (!h->cloud_cnt) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->cloud_cnt, 2 * sizeof(unsigned long long))}));
   C.cnt = h->cloud_cnt;
-  const size_t bytes = (size_t)n_points * p->stride * sizeof(float);
-  if (mem == DIRECT_MEM_HOST && n_points > 0) {
-    CHIP_TRY(hs::grow(h->cloud_in, h->stream, bytes));
-    CHIP_TRY(hipMemcpyAsync(h->cloud_in.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
-    C.xyz = (const float*)h->cloud_in.p;
-  } else {
-    C.xyz = xyz;
-  }
+  if (const direct_status_t rc = cloud_on_device(h, n_points, p->stride, mem, xyz, &C.xyz)) return rc;
   CHIP_TRY(hs::start(h->ev, h->stream));
   hipError_t e = hipMemsetAsync(h->cloud_cnt, 0, 2 * sizeof(unsigned long long), h->stream);
-  if (e == hipSuccess && (p->mode == DIRECT_MAP_REPLACE || !h->have_map)) e = hipMemsetAsync(h->map, 0, (size_t)D.G, h->stream);
+  if (e == hipSuccess && (p->mode == DIRECT_MAP_REPLACE || !h->rs.has_map())) e = hipMemsetAsync(h->map, 0, (size_t)D.G, h->stream);
   if (e == hipSuccess && n_points > 0) {
     const long long lanes = (long long)n_points * (2 * C.s + 1) * (2 * C.s + 1);
     const int blocks = (int)std::min<long long>((lanes + 255) / 256, 1 << 16);  // grid-stride beyond 16.8 M lanes
@@ -1540,33 +1608,29 @@ direct_status_t direct_cluster_map_from_cloud(direct_cluster_handle_t h, const d
   e = hs::drain(h->stream, e);
   // the map has been touched: whatever happened, an earlier table no longer describes it
   if (e != hipSuccess) {
-    h->have_map = false;
+    h->rs.map_lost();
     return cfail(DIRECT_ERR_DEVICE, std::string("map_from_cloud: ") + hipGetErrorString(e));
   }
-  h->have_map = true;
+  h->rs.map_ready();
   if (stats) { stats[0] = n_points; stats[1] = (int64_t)cnt[0]; stats[2] = (int64_t)cnt[1]; stats[3] = occupied; }
   return DIRECT_OK;
 }
 
 direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, uint8_t* map_data) {
   if (!h || !map_data) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  CHIP_TRY(hipMemcpyAsync(map_data, h->map, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                          h->stream));
-  CHIP_TRY(hipStreamSynchronize(h->stream));
-  return DIRECT_OK;
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  return fetch_resident(h, mem, (size_t)h->D.G, map_data, h->map);
 }
 
 direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem,
                                                   const float* xyz, int64_t* stats) {
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (n_points < 0 || (n_points > 0 && !xyz)) return cfail(DIRECT_ERR_INVALID, "n_points negative, or points without a pointer");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (p->mode != DIRECT_SCAN_RESET && p->mode != DIRECT_SCAN_CONTINUE && p->mode != DIRECT_SCAN_ADOPT) return cfail(DIRECT_ERR_INVALID, "unknown mode");
-  if (p->stride != 3 && p->stride != 4) return cfail(DIRECT_ERR_INVALID, "stride must be 3 or 4 floats per point");
-  if (!std::isfinite(p->resolution) || !(p->resolution > 0.0)) return cfail(DIRECT_ERR_INVALID, "resolution must be finite and positive");
+  const char* why = cloud_refusal(n_points, mem, xyz);
+  if (!why && p->mode != DIRECT_SCAN_RESET && p->mode != DIRECT_SCAN_CONTINUE && p->mode != DIRECT_SCAN_ADOPT) why = "unknown mode";
+  if (!why) why = stride_refusal(p->stride);
+  if (!why) why = resolution_refusal(p->resolution);
+  if (why) return cfail(DIRECT_ERR_INVALID, why);
   if (!std::isfinite(p->max_range) || !(p->max_range > 0.0)) return cfail(DIRECT_ERR_INVALID, "max_range must be finite and positive");
   for (int a = 0; a < 3; a++) {
     if (!std::isfinite(p->map_lower[a]) || !std::isfinite(p->map_upper[a])) return cfail(DIRECT_ERR_INVALID, "map_lower / map_upper must be finite");
@@ -1582,7 +1646,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     G.start[a] = mc::axis_index_drop(p->origin[a], p->map_lower[a], p->map_upper[a], G.inv, G.size[a]);  // -1 for a NaN too
     if (G.start[a] < 0) return cfail(DIRECT_ERR_INVALID, "the origin lies outside the map");
   }
-  if (p->mode == DIRECT_SCAN_ADOPT && !h->have_map) return cfail(DIRECT_ERR_INVALID, "DIRECT_SCAN_ADOPT: the handle has no map");
+  if (p->mode == DIRECT_SCAN_ADOPT && !h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "DIRECT_SCAN_ADOPT: the handle has no map");
   if (!(p->max_range * G.inv <= (double)ms::kMaxRangeVox)) return cfail(DIRECT_ERR_UNSUPPORTED, "max_range above 4096 voxels");
   for (int a = 0; a < 3; a++)
     if (p->inflate[a] > ms::kMaxInflate) return cfail(DIRECT_ERR_UNSUPPORTED, "inflate above 64 voxels");
@@ -1594,24 +1658,17 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     for (hipEvent_t& e : h->scan_ev) CHIP_TRY(hipEventCreate(&e));
   S.n = n_points; S.stride = p->stride; S.raw = h->scan_raw; S.cnt = h->scan_cnt;
   if (p->inflate[1] > 0 || p->inflate[2] > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, 2 * cells));
-  const size_t bytes = (size_t)n_points * p->stride * sizeof(float);
-  if (mem == DIRECT_MEM_HOST && n_points > 0) {
-    CHIP_TRY(hs::grow(h->cloud_in, h->stream, bytes));
-    CHIP_TRY(hipMemcpyAsync(h->cloud_in.p, xyz, bytes, hipMemcpyHostToDevice, h->stream));
-    S.xyz = (const float*)h->cloud_in.p;
-  } else {
-    S.xyz = xyz;
-  }
-  const bool had_map = h->have_map;
+  if (const direct_status_t rc = cloud_on_device(h, n_points, p->stride, mem, xyz, &S.xyz)) return rc;
+  const bool had_map = h->rs.has_map();
   auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->scan_ev[k], h->stream) : hipSuccess; };
   CHIP_TRY(hs::start(h->ev, h->stream));
   hipError_t e = hipMemsetAsync(h->scan_cnt, 0, kScanCounters * sizeof(unsigned long long), h->stream);
   if (e == hipSuccess && !had_map) e = hipMemsetAsync(h->map, 0, cells, h->stream);  // the bytes "before" of a handle without a map
   if (e == hipSuccess) {
     if (p->mode == DIRECT_SCAN_ADOPT) e = hipMemcpyAsync(h->scan_raw, h->map, cells, hipMemcpyDeviceToDevice, h->stream);
-    else if (p->mode == DIRECT_SCAN_RESET || !h->have_scan) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
+    else if (p->mode == DIRECT_SCAN_RESET || !h->rs.has_scan_grid()) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
   }
-  h->have_scan = false;  // until the call has ended well
+  h->rs.scan_began();  // no scan grid until the call has ended well
   const int ray_blocks = (int)std::min<long long>((n_points + 255) / 256, kScanMaxBlocks);
   if (e == hipSuccess) e = tick(0);
   if (e == hipSuccess && n_points > 0) {
@@ -1652,17 +1709,10 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   if (e == hipSuccess && h->scan_timing)
     for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&h->scan_ms[k], h->scan_ev[k], h->scan_ev[k + 1]);
   if (e != hipSuccess) {  // the map and the scan grid have been touched: nothing describes them any more
-    h->have_map = false;
-    h->dist_valid = false;
-    h->map_gen++;
+    h->rs.scan_ended(rs::ScanEnd::failed);
     return cfail(DIRECT_ERR_DEVICE, std::string("map_integrate_scan: ") + hipGetErrorString(e));
   }
-  if (changed) {
-    h->dist_valid = false;
-    h->map_gen++;
-  }
-  h->have_map = true;
-  h->have_scan = true;
+  h->rs.scan_ended(changed ? rs::ScanEnd::changed : rs::ScanEnd::unchanged);
   if (stats) {
     stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
     stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
@@ -1672,17 +1722,14 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
 
 direct_status_t direct_cluster_get_scan_grid(direct_cluster_handle_t h, int32_t mem, uint8_t* raw) {
   if (!h || !raw) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!h->have_scan) return cfail(DIRECT_ERR_INVALID, "the handle has no scan grid");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  CHIP_TRY(hipMemcpyAsync(raw, h->scan_raw, (size_t)h->D.G, mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-  CHIP_TRY(hipStreamSynchronize(h->stream));
-  return DIRECT_OK;
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_scan_grid()) return cfail(DIRECT_ERR_INVALID, "the handle has no scan grid");
+  return fetch_resident(h, mem, (size_t)h->D.G, raw, h->scan_raw);
 }
 
 direct_status_t direct_cluster_scan_phase_ms(direct_cluster_handle_t h, float* ms4) {
   if (!h || !ms4) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->scan_timing || !h->have_scan) return cfail(DIRECT_ERR_INVALID, "no timed scan: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
+  if (!h->scan_timing || !h->rs.has_scan_grid()) return cfail(DIRECT_ERR_INVALID, "no timed scan: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
   for (int k = 0; k < 4; k++) ms4[k] = h->scan_ms[k];
   return DIRECT_OK;
 }
@@ -1694,10 +1741,10 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
   if (!h || !seeds) return cfail(DIRECT_ERR_INVALID, "null argument");
   if (batch <= 0 || batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
   if (itr_inflate_max < 0 || itr_cluster_max < 0) return cfail(DIRECT_ERR_INVALID, "negative iteration limit");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
   CHIP_TRY(hipSetDevice(h->cfg.device));
   Dev& D = h->D;
-  h->resident_batch = 0;
+  h->rs.clusters_overwritten();
   CHIP_TRY(hipMemcpyAsync(h->seeds, seeds, (size_t)batch * 3 * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hs::start(h->ev, h->stream));
   int32_t *dv = vertex_idx, *dc = cluster_xyz, *dn = cluster_num, *di = cluster_iters, *dr = rtn;
@@ -1726,7 +1773,7 @@ direct_status_t direct_cluster_polygon_generation_batch(direct_cluster_handle_t 
   }
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("polygon_generation_batch: ") + hipGetErrorString(e));
-  h->resident_batch = batch;
+  h->rs.generation_left(batch);
   return DIRECT_OK;
 }
 
@@ -1735,7 +1782,7 @@ direct_status_t direct_cluster_convex_test(direct_cluster_handle_t h, const uint
                                            uint8_t* can_clu, uint8_t* can_can, uint8_t* accept) {
   if (!h || !inside_data || !candidate_xyz || (!cluster_xyz && n_cluster > 0) || !can_clu)
     return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
   Dev& D = h->D;
   if (n_candidate <= 0 || n_candidate > D.kcap || n_cluster < 0 || n_cluster > D.ccap)
     return cfail(DIRECT_ERR_INVALID, "candidate / cluster count exceeds the handle's capacity");
@@ -1753,7 +1800,7 @@ direct_status_t direct_cluster_convex_test(direct_cluster_handle_t h, const uint
   if (!pack(candidate_xyz, n_candidate, pc) || !pack(cluster_xyz, n_cluster, pk)) return cfail(DIRECT_ERR_INVALID, "voxel outside the map");
   Elem E = {};
   E.n_cluster = n_cluster; E.n_cand = n_candidate; E.live = 1;
-  h->resident_batch = 0;  // element 0's cluster, candidates and flags are overwritten below: the last generation's clusters are gone
+  h->rs.clusters_overwritten();  // element 0's cluster, candidates and flags are overwritten below: the last generation's clusters are gone
   CHIP_TRY(hipMemcpyAsync(h->inside_tmp, inside_data, (size_t)D.G, hipMemcpyHostToDevice, h->stream));
   CHIP_TRY(hipMemcpyAsync(D.cand, pc.data(), (size_t)n_candidate * 4, hipMemcpyHostToDevice, h->stream));
   if (n_cluster) CHIP_TRY(hipMemcpyAsync(D.cluster, pk.data(), (size_t)n_cluster * 4, hipMemcpyHostToDevice, h->stream));
@@ -1788,10 +1835,10 @@ direct_status_t direct_cluster_hull_planes_batch(direct_cluster_handle_t h, int3
   if (batch <= 0 || batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
   if (cluster_xyz && !cluster_num) return cfail(DIRECT_ERR_INVALID, "cluster_xyz without cluster_num");
   if (plane_capacity <= 0 || vertex_capacity <= 0 || !(resolution > 0)) return cfail(DIRECT_ERR_INVALID, "bad capacity / resolution");
-  if (!cluster_xyz && batch > h->resident_batch)
+  if (!cluster_xyz && batch > h->rs.clusters_resident())
     return cfail(DIRECT_ERR_INVALID, "no resident clusters for this batch: call direct_cluster_polygon_generation_batch with at least "
                                      "`batch` seeds first (caller-provided voxels replace the resident clusters)");
-  if (cluster_xyz) h->resident_batch = 0;  // the voxels are packed into the handle's cluster storage: the generation's clusters are gone
+  if (cluster_xyz) h->rs.clusters_overwritten();  // the voxels are packed into the handle's cluster storage: the generation's clusters are gone
   CHIP_TRY(hipSetDevice(h->cfg.device));
   Dev& D = h->D;
   if (const direct_status_t rc = hull_workspace(h)) return rc;
@@ -1833,41 +1880,21 @@ direct_status_t direct_cluster_grid_path_batch(direct_cluster_handle_t h, int32_
   if (!h || !starts || !goals) return cfail(DIRECT_ERR_INVALID, "null argument");
   if (batch <= 0 || batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
   if (path_capacity <= 0 || max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "direct_cluster_set_map has not been called");
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  PathDev& P = h->P;
-  const size_t nb = (size_t)batch;
-  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: workspace allocation: ") + hipGetErrorString(ae));
-  // one block for the read-back ring (a scratch slice, needed whatever `mem` is) and the staging of host outputs (nothing is filled)
-  const size_t cap = (size_t)path_capacity;
-  const size_t sz[5] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t)};
-  void* const user[5] = {path_xyz, path_len, path_cost, stats, rtn};
-  void* dev[5];
+  const PathCall call = {"grid_path_batch", batch, batch, path_capacity, max_rounds, mem, starts, goals, false, 0, 0, nullptr, dist};
+  void* const user[7] = {path_xyz, path_len, path_cost, stats, rtn, nullptr, nullptr};
+  void* dev[7];
   hs::Stage st(mem == DIRECT_MEM_HOST);
-  hs::stage_scratch(st, &P.ring, nb * cap * sizeof(int));
-  for (int i = 0; i < 5; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
-  CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
-  P.cap = (int)cap;
-  const std::vector<int> ends = pack_ends(nb, starts, goals);
-  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
-  CHIP_TRY(hipGetLastError());
-  const long long lim = max_rounds > 0 ? (long long)max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
-  int done = 0;
-  const hipError_t re = path_rounds(h, nb, lim, &done, [&](int r) {
-    hipLaunchKernelGGL(k_path_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, r);
-  });
-  if (re != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: rounds: ") + hipGetErrorString(re));
-  hipLaunchKernelGGL(k_path_trace, dim3(batch), dim3(64), 0, h->stream, P, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
-                     (int32_t*)dev[3], (int32_t*)dev[4]);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::drain(h->stream, download_fields(h, dist, nb, mem, hs::stage_download(st, h->stream, e)));
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  return grid_path_run(h, call, st, [&](PathDev& P, PathClearDev& C) { return path_pair_stage(h, call, st, P, C, user, dev); },
+                       [&](const PathDev& P, const PathClearDev&, int r) {
+                         hipLaunchKernelGGL(k_path_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, r);
+                       },
+                       [&](const PathDev& P, const PathClearDev&, int done) {
+                         hipLaunchKernelGGL(k_path_trace, dim3(batch), dim3(64), 0, h->stream, P, done, (int32_t*)dev[0], (int32_t*)dev[1],
+                                            (double*)dev[2], (int32_t*)dev[3], (int32_t*)dev[4]);
+                       });
 }
 
 direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const direct_plan_check_in_t* in, direct_plan_check_out_t* out) {
@@ -1909,9 +1936,9 @@ direct_status_t direct_cluster_plan_check_batch(direct_cluster_handle_t h, const
 
 direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t cap_vox, int64_t* stats) {
   if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
-  h->field_gen++;  // every call: labels of free_components built with a floor no longer count as describing the field
+  h->rs.field_call_began();  // every call: labels of free_components built with a floor no longer count as describing the field
   if (cap_vox < 0 || cap_vox > df::kMaxCap) return cfail(DIRECT_ERR_INVALID, "cap_vox outside [0, 1024]");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const Dev& D = h->D;
   if (!h->dist[0]) {  // all or nothing
@@ -1919,7 +1946,7 @@ direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t
                                                     hs::want(&h->dist_cnt, 2 * sizeof(unsigned long long))});
     if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: allocation: ") + hipGetErrorString(ae));
   }
-  h->dist_valid = false;
+  h->rs.field_build_began();
   DistDev A = {};
   A.map = h->map; A.a = h->dist[0]; A.b = h->dist[1];
   A.X = D.max_x; A.Y = D.max_y; A.Z = D.max_z; A.G = D.G; A.cap2 = df::cap2_of(cap_vox);
@@ -1933,29 +1960,23 @@ direct_status_t direct_cluster_distance_field(direct_cluster_handle_t h, int32_t
   if (e == hipSuccess && stats) e = hipMemcpyAsync(cnt, h->dist_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("distance_field: ") + hipGetErrorString(e));
-  h->dist_valid = true;
-  h->dist_cap2 = A.cap2;
-  h->dist_serial++;
+  h->rs.field_built(A.cap2);
   if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)(int32_t)(cnt[1] & 0xffffffffull); }
   return DIRECT_OK;
 }
 
 direct_status_t direct_cluster_get_distance_field(direct_cluster_handle_t h, int32_t mem, int32_t* d2) {
   if (!h || !d2) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (!h->dist_valid) return cfail(DIRECT_ERR_INVALID, "no valid distance field: call direct_cluster_distance_field after the map changes");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  CHIP_TRY(hipMemcpyAsync(d2, h->dist[0], (size_t)h->D.G * sizeof(int32_t), mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
-                          h->stream));
-  CHIP_TRY(hipStreamSynchronize(h->stream));
-  return DIRECT_OK;
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (const char* why = h->rs.field_refusal(0, 0)) return cfail(DIRECT_ERR_INVALID, why);
+  return fetch_resident(h, mem, (size_t)h->D.G * sizeof(int32_t), d2, h->dist[0]);
 }
 
 direct_status_t direct_cluster_plan_clearance_batch(direct_cluster_handle_t h, const direct_plan_clear_in_t* in, direct_plan_clear_out_t* out) {
   const char* why = plan_rows_refusal(h, in, out);
   if (!why) why = plan_map_refusal(h, in, in->radius, "radius must be finite and not negative");
-  if (!why && !h->dist_valid) why = "no valid distance field: call direct_cluster_distance_field after the map changes";
+  if (!why) why = h->rs.field_refusal(0, 0);
   if (why) return cfail(DIRECT_ERR_INVALID, why);
   // host arrays go through one staging block of the call's own; seg_clearance alone is filled (0xff: entries past n_seg read NaN)
   hs::Stage st(in->mem == DIRECT_MEM_HOST);
@@ -1994,7 +2015,7 @@ direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t
   if (const direct_status_t rc = cube_corridor_refusal(h, in, out, min_d2 < 0 ? "min_d2 must not be negative" : nullptr)) return rc;
   const bool neutral = cc::floor_neutral(min_d2);  // the map's own table: the field is not looked at
   if (!neutral)
-    if (const char* why = clear_field_refusal(h, min_d2, 0)) return cfail(DIRECT_ERR_INVALID, why);
+    if (const char* why = h->rs.field_refusal(min_d2, 0)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   Dev D = h->D;
   const size_t entries = (size_t)(D.max_x + 1) * D.sat_yz;
@@ -2004,9 +2025,8 @@ direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t
       const hipError_t ae = hs::alloc_all(h->allocs, {hs::want(&h->floor_tab[0], entries * sizeof(int)), hs::want(&h->floor_tab[1], entries * sizeof(int))});
       if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("cube_corridor_clear_batch: table allocation: ") + hipGetErrorString(ae));
     }
-    slot = cc::floor_slot_choose(h->floor_slot, cc::kFloorSlots, min_d2, h->dist_serial, &hit);
+    slot = h->rs.floor_chosen(min_d2, &hit);  // a miss: the slot holds nothing until its build has drained without an error
     D.sat = h->floor_tab[slot];
-    if (!hit) h->floor_slot[slot].valid = 0;  // until its build has drained without an error
   }
   int count = 0;  // the table's last entry is the sum over the whole map
   const bool fetch = neutral ? info != nullptr : !hit;
@@ -2016,13 +2036,15 @@ direct_status_t direct_cluster_cube_corridor_clear_batch(direct_cluster_handle_t
     for (int axis = 2; axis >= 0; axis--) hipLaunchKernelGGL(k_sat_scan, dim3(256), dim3(256), 0, h->stream, D, axis);
     return hipGetLastError();
   }, [&] { return fetch ? hipMemcpyAsync(&count, D.sat + (entries - 1), sizeof(int), hipMemcpyDeviceToHost, h->stream) : hipSuccess; });
-  if (rc != DIRECT_OK) return rc;
-  if (!neutral) {
-    cc::FloorSlot& s = h->floor_slot[slot];
-    if (!hit) { s.min_d2 = min_d2; s.serial = h->dist_serial; s.count = count; s.valid = 1; }
-    s.used = ++h->floor_clock;
+  if (rc != DIRECT_OK) {
+    if (!hit) h->rs.floor_build_failed(slot);
+    return rc;
   }
-  if (info) { info[0] = hit ? 0 : 1; info[1] = neutral ? count : h->floor_slot[slot].count; }
+  if (!neutral) {
+    if (!hit) h->rs.floor_built(slot, min_d2, count);
+    h->rs.floor_used(slot);
+  }
+  if (info) { info[0] = hit ? 0 : 1; info[1] = neutral ? count : h->rs.floor_count(slot); }
   return DIRECT_OK;
 }
 
@@ -2031,7 +2053,7 @@ direct_status_t direct_cluster_corridor_batch(direct_cluster_handle_t h, const d
   if (const direct_status_t rc = cube_corridor_refusal(h, in, out, in && in->itr_cluster_max < 0 ? "itr_cluster_max must not be negative" : nullptr))
     return rc;
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  h->resident_batch = 0;  // the chunks' generations run in the handle's cluster storage: the last generation's clusters are gone
+  h->rs.clusters_overwritten();  // the chunks' generations run in the handle's cluster storage: the last generation's clusters are gone
   if (const direct_status_t rc = hull_workspace(h)) return rc;
   const Dev& D = h->D;
   const size_t B = (size_t)in->batch, slots = B * (size_t)in->path_capacity, segs = B * (size_t)in->seg_capacity;
@@ -2118,48 +2140,26 @@ direct_status_t direct_cluster_grid_path_clear_batch(direct_cluster_handle_t h, 
   // what the arguments alone decide comes first, then what the handle holds
   if (in->batch <= 0) return cfail(DIRECT_ERR_INVALID, "batch must be positive");
   if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
-  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!mem_kind(in->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
   if (const char* why = clear_args_refusal(in->min_d2, in->n_penalty, in->penalty)) return cfail(DIRECT_ERR_INVALID, why);
   if (in->batch > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "batch exceeds the handle's max_batch");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (const char* why = clear_field_refusal(h, in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (const char* why = h->rs.field_refusal(in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: workspace allocation: ") + hipGetErrorString(ae));
-  if (const direct_status_t us = upload_penalty(h, in->n_penalty, in->penalty, "grid_path_clear_batch"); us != DIRECT_OK) return us;
-  PathDev& P = h->P;
-  PathClearDev C = clear_dev(h, in->min_d2, in->n_penalty);
-  // one block for the two read-back rings (scratch slices, needed whatever `mem` is) and the staging of host outputs
   const int batch = in->batch;
-  const size_t nb = (size_t)batch, cap = (size_t)in->path_capacity;
-  const size_t sz[7] = {nb * cap * 3 * sizeof(int32_t), nb * sizeof(int32_t), nb * sizeof(double), nb * 2 * sizeof(int32_t), nb * sizeof(int32_t),
-                        nb * cap * sizeof(int32_t), nb * sizeof(int32_t)};
+  const PathCall call = {"grid_path_clear_batch", batch, batch, in->path_capacity, in->max_rounds, in->mem, in->starts, in->goals, true,
+                         in->min_d2, in->n_penalty, in->penalty, out->dist};
   void* const user[7] = {out->path_xyz, out->path_len, out->path_cost, out->stats, out->rtn, out->path_d2, out->path_min_d2};
   void* dev[7];
   hs::Stage st(in->mem == DIRECT_MEM_HOST);
-  hs::stage_scratch(st, &P.ring, nb * cap * sizeof(int));
-  hs::stage_scratch(st, &C.ring_d2, nb * cap * sizeof(int));
-  for (int i = 0; i < 7; i++) hs::stage_out(st, &dev[i], user[i], sz[i]);
-  CHIP_TRY(hs::stage_upload(st, h->path_out, h->stream));
-  P.cap = (int)cap;
-  const std::vector<int> ends = pack_ends(nb, in->starts, in->goals);
-  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), nb * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), batch), dim3(256), 0, h->stream, P);
-  CHIP_TRY(hipGetLastError());
-  const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
-  int done = 0;
-  const hipError_t re = path_rounds(h, nb, lim, &done, [&](int r) {
-    hipLaunchKernelGGL(k_path_clear_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, C, r);
-  });
-  if (re != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: rounds: ") + hipGetErrorString(re));
-  hipLaunchKernelGGL(k_path_clear_trace, dim3(batch), dim3(64), 0, h->stream, P, C, done, (int32_t*)dev[0], (int32_t*)dev[1], (double*)dev[2],
-                     (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (int32_t*)dev[6]);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::drain(h->stream, download_fields(h, out->dist, nb, in->mem, hs::stage_download(st, h->stream, e)));
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_clear_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  return grid_path_run(h, call, st, [&](PathDev& P, PathClearDev& C) { return path_pair_stage(h, call, st, P, C, user, dev); },
+                       [&](const PathDev& P, const PathClearDev& C, int r) {
+                         hipLaunchKernelGGL(k_path_clear_relax, dim3(P.ntiles, batch), dim3(256), 0, h->stream, P, C, r);
+                       },
+                       [&](const PathDev& P, const PathClearDev& C, int done) {
+                         hipLaunchKernelGGL(k_path_clear_trace, dim3(batch), dim3(64), 0, h->stream, P, C, done, (int32_t*)dev[0], (int32_t*)dev[1],
+                                            (double*)dev[2], (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5], (int32_t*)dev[6]);
+                       });
 }
 
 direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, const direct_grid_path_fan_in_t* in,
@@ -2169,7 +2169,7 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   if (in->n_src < 1) return cfail(DIRECT_ERR_INVALID, "n_src must be positive");
   if (in->n_goal < 1) return cfail(DIRECT_ERR_INVALID, "n_goal must be positive");
   if (in->path_capacity <= 0 || in->max_rounds < 0) return cfail(DIRECT_ERR_INVALID, "path_capacity must be positive, max_rounds not negative");
-  if (in->mem != DIRECT_MEM_HOST && in->mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!mem_kind(in->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
   if (const char* why = clear_args_refusal(in->min_d2, in->n_penalty, in->penalty)) return cfail(DIRECT_ERR_INVALID, why);
   if (!in->goal_src && in->n_src != 1) return cfail(DIRECT_ERR_INVALID, "a NULL goal_src requires n_src == 1");
   if (in->goal_src)
@@ -2179,15 +2179,13 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   if (!clear && (out->path_d2 || out->path_min_d2))
     return cfail(DIRECT_ERR_INVALID, "path_d2 and path_min_d2 must be NULL in neutral mode (min_d2 <= 1, n_penalty == 0)");
   if (in->n_src > h->cfg.max_batch) return cfail(DIRECT_ERR_INVALID, "n_src exceeds the handle's max_batch");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
   if (clear)
-    if (const char* why = clear_field_refusal(h, in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
+    if (const char* why = h->rs.field_refusal(in->min_d2, in->n_penalty)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
-  if (const hipError_t ae = path_workspace(h); ae != hipSuccess)
-    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ae));
-  if (const direct_status_t us = upload_penalty(h, in->n_penalty, in->penalty, "grid_path_fan_batch"); us != DIRECT_OK) return us;
-  PathDev& P = h->P;
-  const PathClearDev C = clear ? clear_dev(h, in->min_d2, in->n_penalty) : PathClearDev{};
+  // k_path_init's (start, goal) of a field = (source, source)
+  const PathCall call = {"grid_path_fan_batch", in->n_src, in->n_goal, in->path_capacity, in->max_rounds, in->mem, in->sources, in->sources, clear,
+                         in->min_d2, in->n_penalty, in->penalty, out->dist};
   const size_t ns = (size_t)in->n_src, ng = (size_t)in->n_goal, cap = (size_t)in->path_capacity;
   // the goals, their sources and the grouping by source (a counting sort: the goals of a source in the caller's order), one array
   std::vector<int> meta(3 * ng + ng + ng + ns + 1);
@@ -2201,7 +2199,6 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
     std::vector<int> at(m_off, m_off + ns);
     for (size_t j = 0; j < ng; j++) m_order[at[m_src[j]]++] = (int)j;
   }
-  const std::vector<int> ends = pack_ends(ns, in->sources, in->sources);  // k_path_init's (start, goal) = (source, source)
   // Two blocks, both or neither: the workspace (host inputs and scratch, whatever `mem` is) and the staging of host outputs.
   FanDev F = {};
   F.n_src = in->n_src; F.n_goal = in->n_goal;
@@ -2216,26 +2213,21 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
   void* const user[7] = {out->path_xyz, out->path_len, out->path_cost, out->rtn, out->path_d2, out->path_min_d2, out->stats};
   void* dev[7];
   for (int i = 0; i < 7; i++) hs::stage_out(so, &dev[i], user[i], sz[i]);
-  hipError_t ue = hs::stage_upload(sw, h->fan_ws, h->stream);
-  if (ue == hipSuccess) ue = hs::stage_upload(so, h->fan_out, h->stream);
-  if (ue != hipSuccess) {
-    (void)hipStreamSynchronize(h->stream);
-    hs::release(h->fan_ws);
-    hs::release(h->fan_out);
-    return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ue));
-  }
-  F.goals = d_meta; F.gsrc = d_meta + 3 * ng; F.order = F.gsrc + ng; F.off = F.order + ng;
-  P.cap = (int)cap;
-  CHIP_TRY(hipMemcpyAsync(P.ends, ends.data(), ns * 6 * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CHIP_TRY(hs::start(h->ev, h->stream));
-  hipLaunchKernelGGL(k_path_init, dim3(std::min((P.G + 255) / 256, 2048), in->n_src), dim3(256), 0, h->stream, P);
-  CHIP_TRY(hipGetLastError());
-  const long long lim = in->max_rounds > 0 ? (long long)in->max_rounds : gp::default_max_rounds(P.X, P.Y, P.Z);
-  int done = 0;
-  // k_fan_bound goes in front of every round, or of every batch of rounds (fan_bound_every: 1 or gp::kFanRoundsPerCheck, and a
-  // batch starts at a multiple of that)
-  const dim3 tiles(P.ntiles, in->n_src);
-  hipError_t e = path_rounds(h, ns, lim, &done, [&](int r) {
+  return grid_path_run(h, call, so, [&](PathDev&, PathClearDev&) -> direct_status_t {
+    hipError_t ue = hs::stage_upload(sw, h->fan_ws, h->stream);
+    if (ue == hipSuccess) ue = hs::stage_upload(so, h->fan_out, h->stream);
+    if (ue != hipSuccess) {
+      (void)hipStreamSynchronize(h->stream);
+      hs::release(h->fan_ws);
+      hs::release(h->fan_out);
+      return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: workspace allocation: ") + hipGetErrorString(ue));
+    }
+    F.goals = d_meta; F.gsrc = d_meta + 3 * ng; F.order = F.gsrc + ng; F.off = F.order + ng;
+    return DIRECT_OK;
+  }, [&](const PathDev& P, const PathClearDev& C, int r) {
+    // k_fan_bound goes in front of every round, or of every batch of rounds (fan_bound_every: 1 or gp::kFanRoundsPerCheck, and a
+    // batch starts at a multiple of that)
+    const dim3 tiles(P.ntiles, in->n_src);
     const bool bound = r % h->fan_bound_every == 0;
     if (clear) {
       if (bound) hipLaunchKernelGGL(k_fan_bound<true>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
@@ -2244,8 +2236,7 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
       if (bound) hipLaunchKernelGGL(k_fan_bound<false>, dim3(F.n_src), dim3(kFanBoundLanes), 0, h->stream, P, C, F);
       hipLaunchKernelGGL(k_fan_relax<false>, tiles, dim3(256), 0, h->stream, P, C, (const double*)F.bound, r);
     }
-  });
-  if (e == hipSuccess) {
+  }, [&](const PathDev& P, const PathClearDev& C, int done) {
     if (clear)
       hipLaunchKernelGGL(k_fan_trace<true>, dim3(in->n_goal), dim3(64), 0, h->stream, P, C, F, done, (int32_t*)dev[0], (int32_t*)dev[1],
                          (double*)dev[2], (int32_t*)dev[3], (int32_t*)dev[4], (int32_t*)dev[5]);
@@ -2253,21 +2244,16 @@ direct_status_t direct_cluster_grid_path_fan_batch(direct_cluster_handle_t h, co
       hipLaunchKernelGGL(k_fan_trace<false>, dim3(in->n_goal), dim3(64), 0, h->stream, P, C, F, done, (int32_t*)dev[0], (int32_t*)dev[1],
                          (double*)dev[2], (int32_t*)dev[3], (int32_t*)nullptr, (int32_t*)nullptr);
     if (dev[6]) hipLaunchKernelGGL(k_fan_stats, dim3(1), dim3(64), 0, h->stream, P, in->n_src, (int32_t*)dev[6]);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::drain(h->stream, download_fields(h, out->dist, ns, in->mem, hs::stage_download(so, h->stream, e)));
-  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("grid_path_fan_batch: ") + hipGetErrorString(e));
-  return DIRECT_OK;
+  });
 }
 
 direct_status_t direct_cluster_free_components(direct_cluster_handle_t h, int32_t min_d2, int64_t* stats) {
   if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
   if (min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
   const int32_t floor = fc::normal_floor(min_d2);
   if (floor)
-    if (const char* why = clear_field_refusal(h, floor, 0)) return cfail(DIRECT_ERR_INVALID, why);
+    if (const char* why = h->rs.field_refusal(floor, 0)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const Dev& D = h->D;
   if (!h->comp_label) {  // all or nothing
@@ -2275,7 +2261,7 @@ direct_status_t direct_cluster_free_components(direct_cluster_handle_t h, int32_
                                                     hs::want(&h->comp_cnt, 4 * sizeof(unsigned long long))});
     if (ae != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("free_components: allocation: ") + hipGetErrorString(ae));
   }
-  h->comp_key.valid = 0;
+  h->rs.label_build_began();
   CompDev A = {};
   A.map = h->map; A.d2 = floor ? h->dist[0] : nullptr; A.label = h->comp_label; A.size = h->comp_size; A.cnt = h->comp_cnt;
   A.X = D.max_x; A.Y = D.max_y; A.Z = D.max_z; A.G = D.G; A.min_d2 = floor;
@@ -2290,22 +2276,18 @@ direct_status_t direct_cluster_free_components(direct_cluster_handle_t h, int32_
   e = hs::drain(h->stream, e);
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("free_components: ") + hipGetErrorString(e));
   if (cnt[3]) return cfail(DIRECT_ERR_DEVICE, "free_components: a union-find loop passed its trip bound (error word " + std::to_string(cnt[3]) + ")");
-  h->comp_key = fc::Key{h->map_gen, h->field_gen, floor, 1};
+  h->rs.labels_built(floor);
   if (stats) { stats[0] = (int64_t)cnt[0]; stats[1] = (int64_t)cnt[1]; stats[2] = fc::stat_size(cnt[2]); stats[3] = fc::stat_label(cnt[2]); }
   return DIRECT_OK;
 }
 
 direct_status_t direct_cluster_get_free_components(direct_cluster_handle_t h, int32_t mem, int32_t* label, int32_t* size, int32_t* min_d2_built) {
   if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
-  if (mem != DIRECT_MEM_HOST && mem != DIRECT_MEM_DEVICE) return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (!fc::key_serves(h->comp_key, h->map_gen, h->field_gen)) return cfail(DIRECT_ERR_INVALID, kCompStale);
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  const hipMemcpyKind kind = mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  if (label) CHIP_TRY(hipMemcpyAsync(label, h->comp_label, (size_t)h->D.G * sizeof(int32_t), kind, h->stream));
-  if (size) CHIP_TRY(hipMemcpyAsync(size, h->comp_size, (size_t)h->D.G * sizeof(int32_t), kind, h->stream));
-  CHIP_TRY(hipStreamSynchronize(h->stream));
-  if (min_d2_built) *min_d2_built = h->comp_key.floor;
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.labels_serve()) return cfail(DIRECT_ERR_INVALID, kCompStale);
+  if (const direct_status_t rc = fetch_resident(h, mem, (size_t)h->D.G * sizeof(int32_t), label, h->comp_label, size, h->comp_size)) return rc;
+  if (min_d2_built) *min_d2_built = h->rs.labels_floor();
   return DIRECT_OK;
 }
 
@@ -2313,12 +2295,11 @@ direct_status_t direct_cluster_reachable_batch(direct_cluster_handle_t h, const 
   if (!h || !in || !out || !in->starts || !in->goals) return cfail(DIRECT_ERR_INVALID, "null argument");
   // what the arguments alone decide comes first, then what the handle holds
   if (in->n <= 0) return cfail(DIRECT_ERR_INVALID, "n must be positive");
-  if ((in->mem_in != DIRECT_MEM_HOST && in->mem_in != DIRECT_MEM_DEVICE) || (out->mem != DIRECT_MEM_HOST && out->mem != DIRECT_MEM_DEVICE))
-    return cfail(DIRECT_ERR_INVALID, "mem is neither DIRECT_MEM_HOST nor DIRECT_MEM_DEVICE");
+  if (!mem_kind(in->mem_in) || !mem_kind(out->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
   if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
-  if (!h->have_map) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
-  if (!fc::key_serves(h->comp_key, h->map_gen, h->field_gen)) return cfail(DIRECT_ERR_INVALID, kCompStale);
-  if (fc::normal_floor(in->min_d2) != h->comp_key.floor)
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.labels_serve()) return cfail(DIRECT_ERR_INVALID, kCompStale);
+  if (fc::normal_floor(in->min_d2) != h->rs.labels_floor())
     return cfail(DIRECT_ERR_INVALID, "min_d2 differs from the floor the free components were built with");
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const size_t n = (size_t)in->n;
