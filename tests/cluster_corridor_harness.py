@@ -1,4 +1,5 @@
-"""g++ build of direct_amd/csrc/cluster_corridor_math.h as a program - TEST INFRASTRUCTURE of tests/test_cluster_corridor_cpp.py.
+"""g++ build of direct_amd/csrc/cluster_corridor_math.h as a program - TEST INFRASTRUCTURE of tests/test_cluster_corridor_cpp.py,
+tests/test_gpu_cluster_corridor.py and the stride tests (tests/corridor_stride_lib.py).
 The program emulates a whole direct_cluster_corridor_batch call the way the host loop and the kernels of cluster_corridor.h run it:
 rounds of advance (every row until it is due or done, with a serial plane test on the double stack), unique (the header's own
 serial statement of the de-duplication), chunks of at most `chunk` unique seeds, append, and emit after the last round.  The one
@@ -6,15 +7,13 @@ thing it does not compute is a polytope: generation + hull of a seed voxel are l
 Python fills from the CPU oracles (oracle.clusterapi.polygon_generation + oracle.hullapi.hull_planes) - so a test can also plant
 a failing seed.  A seed that is due and not in the table ends the program with status 3.
 This file also holds what the CPU and the GPU tests share: the rows, the oracle's corridors and the comparison."""
-import os
-import subprocess
-
 import numpy as np
 
 from oracle import clusterapi, corridor_walk, hullapi
+from tests import corridor_lib as lib
+from tests import cpp_program as cpp
 from tests import cube_corridor_harness as ch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, OVERFLOW, BAD_PATH, NO_POLYTOPE, TOO_MANY_PLANES = 0, 1, 2, 3, 4
 RES, LOWER, DIMS = ch.RES, ch.LOWER, ch.DIMS
 CAP, SEG, PMAX = 40, 12, 20          # path_capacity, seg_capacity and p_max of the tests (most planes of a polytope here: 16)
@@ -150,43 +149,24 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    src = os.path.join(str(workdir), "cluster_corridor_harness.cpp")
-    exe = os.path.join(str(workdir), "cluster_corridor_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), cpp.compile_program(workdir, "cluster_corridor_harness", HARNESS, ["-Wno-unknown-pragmas"])
 
 
 def corridors(harness, paths, path_len, table, pop_back=True, seg_capacity=SEG, p_max=PMAX, dtype=np.float64, chunk=64, res=RES, lower=LOWER,
               dims=DIMS):
     """the outputs of ClusterGenerator.cluster_corridors for the same arguments on a handle with max_batch = chunk, polytopes from
     `table`: voxel (x, y, z) -> dict(gen_ok, rc, n_planes, planes [n][4], center [3])"""
-    d, exe = harness
     paths, path_len = np.ascontiguousarray(paths, np.int32), np.ascontiguousarray(path_len, np.int32)
     B, cap = paths.shape[0], paths.shape[1]
     S, P, real = int(seg_capacity), int(p_max), np.dtype(dtype)
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    with open(fin, "wb") as f:
-        np.array(list(dims) + [B, cap, int(pop_back), S, P, int(real == np.float32), int(chunk), len(table), 0], np.int32).tofile(f)
-        np.array([res] + list(lower), np.float64).tofile(f)
-        paths.tofile(f)
-        path_len.tofile(f)
-        for key, t in table.items():
-            pl = np.ascontiguousarray(t["planes"], np.float64).reshape(-1, 4)
-            np.array(list(key) + [int(t["gen_ok"]), int(t["rc"]), len(pl)], np.int32).tofile(f)
-            pl.tofile(f)
-            np.ascontiguousarray(t["center"], np.float64).tofile(f)
-    subprocess.check_call([exe, fin, fout])
-    raw = open(fout, "rb").read()
-    os.remove(fout)
-    out, off = {}, 0
-    for k, dt, shape in (("n_seg", np.int32, (B,)), ("n_planes", np.int32, (B, S)), ("planes", real, (B, S, P, 4)), ("seeds", real, (B, S, 3)),
-                         ("centers", real, (B, S, 3)), ("rtn", np.int32, (B,)), ("stats", np.int64, (4,))):
-        n = int(np.prod(shape)) * np.dtype(dt).itemsize
-        out[k], off = np.frombuffer(raw[off:off + n], dt).reshape(shape).copy(), off + n
-    assert off == len(raw)
+    arrays = [paths, path_len]
+    for key, t in table.items():
+        pl = np.ascontiguousarray(t["planes"], np.float64).reshape(-1, 4)
+        arrays += [np.array(list(key) + [int(t["gen_ok"]), int(t["rc"]), len(pl)], np.int32), pl, np.asarray(t["center"], np.float64)]
+    raw = cpp.exchange(harness, list(dims) + [B, cap, int(pop_back), S, P, int(real == np.float32), int(chunk), len(table), 0],
+                       [res] + list(lower), arrays)
+    out = cpp.unpack(raw, (("n_seg", np.int32, (B,)), ("n_planes", np.int32, (B, S)), ("planes", real, (B, S, P, 4)), ("seeds", real, (B, S, 3)),
+                           ("centers", real, (B, S, 3)), ("rtn", np.int32, (B,)), ("stats", np.int64, (4,))))
     out["stats"] = dict(zip(("rounds", "due_seeds", "unique_seeds", "pops"), (int(v) for v in out["stats"])))
     return out
 
@@ -194,9 +174,10 @@ def corridors(harness, paths, path_len, table, pop_back=True, seg_capacity=SEG, 
 # ---- what the CPU and the GPU tests share ---------------------------------------------------------------------------------
 
 def inside_rows():
-    """the paths of the named cases that lie inside the map, and the eight random walks"""
-    paths = [p for c in ch.named_cases() if c["name"] != "outside_voxel" for p in c["paths"]]
-    return [np.asarray(p, np.int32).reshape(-1, 3) for p in paths] + ch.random_paths(ch.crafted_map(), 8, seed=9)
+    """the paths of the named cases that lie inside the map, and eight random walks: the first 23 of the 40 rows"""
+    rows = lib.named_rows() + ch.random_paths(ch.crafted_map(), 8, seed=9)
+    assert len(rows) == 23 and all(np.array_equal(a, b) for a, b in zip(rows, lib.rows40()))
+    return rows
 
 
 def shared_start_rows():
@@ -240,9 +221,3 @@ def assert_rows_equal_oracle(got, want, rows):
             assert np.array_equal(got["centers"][b, s], c["center"]) and np.array_equal(got["seeds"][b, s], c["seed_coord"]), (b, s)
         for key in ("n_planes", "planes", "seeds", "centers"):
             assert not got[key][b, k:].any(), (b, key)
-
-
-def same(a, b, keys=KEYS):
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), k

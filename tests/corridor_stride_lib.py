@@ -9,9 +9,15 @@ Nothing here is computed by the device: polytopes come from the CPU oracles, cor
 import numpy as np
 
 from tests import cluster_corridor_harness as kh
+from tests import cube_corridor_clear_harness as cl
 from tests import cube_corridor_harness as ch
 
 RES, LOWER, DIMS = ch.RES, ch.LOWER, ch.DIMS
+
+
+def build_harness(which, tmp_path_factory, tag=""):
+    """what the module-scoped harness fixtures of both stride test files return: which is "cluster", "cube" or "clear" """
+    return {"cluster": kh, "cube": ch, "clear": cl}[which].build(tmp_path_factory.mktemp("corridor_strides_%s%s" % (tag, which)))
 
 # ---- wide: more than 64 planes -------------------------------------------------------------------------------------------
 

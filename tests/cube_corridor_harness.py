@@ -1,32 +1,39 @@
-"""g++ build of direct_amd/csrc/cube_corridor_math.h as a program - TEST INFRASTRUCTURE of tests/test_cube_corridor_cpp.py,
-tests/test_cube_corridor_restatement.py, tests/test_gpu_cube_corridor.py and tools/cube_corridor_bench.py.  The program builds the
-summed-area table of the map (bytes == 1, the library's layout) and runs the header's functions serially:
+"""g++ build of direct_amd/csrc/cube_corridor_math.h and cube_corridor_clear_math.h as ONE program - TEST INFRASTRUCTURE of
+tests/test_cube_corridor_cpp.py, tests/test_cube_corridor_restatement.py, tests/test_gpu_cube_corridor.py,
+tools/cube_corridor_bench.py and, through tests/cube_corridor_clear_harness.py, of the radius-aware call's tests.  The program
+restates direct_cluster_cube_corridor_batch and direct_cluster_cube_corridor_clear_batch serially on a summed-area table (the
+library's layout) that one header word has filled in one of two ways, each the witness of the other:
+  map    inclusion-exclusion over the map's bytes == 1
+  floor  entry by entry through the clear header's index arithmetic - the map's own table when the floor is neutral, else the
+         floor table of the distance field -, then running sums along z, y, x as k_sat_scan takes them
+and runs the headers' functions:
   cubes      the cube of a list of seed voxels, with the number of table queries each took
   polytopes  planes, centre and degenerate flag of a list of cubes
-  corridors  a whole direct_cluster_cube_corridor_batch call: every output of the C-ABI, in either dtype, with its return codes
+  table      the table in use, every entry
+  corridors  a whole call: every output of the C-ABI, in either dtype, with its return codes, then the queries per path voxel
 This file also holds the map and the named paths that the CPU and the GPU tests share."""
-import os
-import subprocess
-
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import cpp_program as cpp
+
+ROOT = cpp.ROOT
 OK, OVERFLOW, BAD_PATH = 0, 1, 2
 NO_CUBE = -1
 RES, LOWER = 0.2, np.array([-2.4, -2.0, 0.0])
 DIMS = (24, 20, 12)
+CUBES, POLYTOPES, TABLE, CORRIDORS = 0, 1, 2, 3   # the program's modes
+FROM_MAP, FROM_FLOOR = 0, 1                       # and its two ways to fill the table
 
 HARNESS = r'''
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+#include "cube_corridor_clear_math.h"
 #include "cube_corridor_math.h"
 namespace cc = direct::cubecor;
-struct Map { int X, Y, Z, sz, syz; std::vector<uint8_t> m; std::vector<int> sat; };
-static void build_sat(Map& M) {
-  M.sz = M.Z + 1; M.syz = (M.Y + 1) * M.sz;
-  M.sat.assign((size_t)(M.X + 1) * M.syz, 0);
+struct Map { int X, Y, Z, sz, syz; std::vector<uint8_t> m; std::vector<int32_t> d2; std::vector<int> sat; };
+static void fill_from_map(Map& M) {
   for (int x = 1; x <= M.X; x++)
     for (int y = 1; y <= M.Y; y++)
       for (int z = 1; z <= M.Z; z++) {
@@ -34,6 +41,22 @@ static void build_sat(Map& M) {
         M.sat[x * M.syz + y * M.sz + z] = (M.m[((x - 1) * M.Y + (y - 1)) * M.Z + (z - 1)] == 1 ? 1 : 0) + S(x - 1, y, z) + S(x, y - 1, z) + S(x, y, z - 1) -
                                           S(x - 1, y - 1, z) - S(x - 1, y, z - 1) - S(x, y - 1, z - 1) + S(x - 1, y - 1, z - 1);
       }
+}
+static void fill_from_floor(Map& M, int min_d2) {
+  for (int i = 0; i < (int)M.sat.size(); i++) {
+    if (cc::floor_neutral(min_d2)) {  // the map's own table: the field is not looked at
+      const int v = cc::floor_entry_voxel(i, M.Y, M.Z);
+      M.sat[i] = v >= 0 && M.m[v] == 1 ? 1 : 0;
+    } else {
+      M.sat[i] = cc::floor_entry(M.d2.data(), i, M.Y, M.Z, min_d2);
+    }
+  }
+  const int st[3] = {M.syz, M.sz, 1};
+  for (int axis = 2; axis >= 0; axis--)  // running sums along z, then y, then x
+    for (size_t i = 0; i < M.sat.size(); i++) {
+      const int c[3] = {(int)(i / M.syz), (int)(i % M.syz) / M.sz, (int)(i % M.sz)};
+      if (c[axis] > 0) M.sat[i] += M.sat[i - st[axis]];
+    }
 }
 static int box(const Map& M, int x0, int y0, int z0, int x1, int y1, int z1) {
   auto S = [&](int a, int b, int c) { return M.sat[a * M.syz + b * M.sz + c]; };
@@ -54,22 +77,33 @@ static void wr_real(FILE* f, const std::vector<double>& v, int f32) {
   for (size_t i = 0; i < v.size(); i++) w[i] = (float)v[i];
   wr(f, w);
 }
-// in: int32 X, Y, Z, mode, n, cap, itr, pop_back, seg_cap, p_max, f32, 0; float64 res, lower[3]; uint8 map[G]; then per mode (below)
+// in: int32 X, Y, Z, mode, n, cap, itr, pop_back, seg_cap, p_max, f32, min_d2, fill; float64 res, lower[3]; uint8 map[G];
+// with fill == 1 int32 d2[G]; then per mode (below)
 int main(int argc, char** argv) {
   if (argc < 3) return 2;
   FILE* f = fopen(argv[1], "rb");
-  int h[12];
+  int h[13];
   double g[4];
-  if (!f || fread(h, 4, 12, f) != 12 || fread(g, 8, 4, f) != 4) return 1;
+  if (!f || fread(h, 4, 13, f) != 13 || fread(g, 8, 4, f) != 4) return 1;
   Map M;
   M.X = h[0]; M.Y = h[1]; M.Z = h[2];
-  const int mode = h[3], n = h[4], cap = h[5], itr = h[6], pop_back = h[7], S = h[8], P = h[9], f32 = h[10];
+  const int mode = h[3], n = h[4], cap = h[5], itr = h[6], pop_back = h[7], S = h[8], P = h[9], f32 = h[10], min_d2 = h[11], fill = h[12];
   const double res = g[0], *lower = g + 1;
   M.m.resize((size_t)M.X * M.Y * M.Z);
   rd(f, M.m);
-  build_sat(M);
+  M.sz = M.Z + 1; M.syz = (M.Y + 1) * M.sz;
+  M.sat.assign((size_t)(M.X + 1) * M.syz, 0);
+  if (fill == 1) {
+    M.d2.resize(M.m.size());
+    rd(f, M.d2);
+    fill_from_floor(M, min_d2);
+  } else {
+    fill_from_map(M);
+  }
   FILE* o = fopen(argv[2], "wb");
-  if (mode == 0) {  // int32 seeds[n][3] -> int32 cube[n][6], queries[n]
+  if (mode == 2) {  // -> int32 table[(X+1)(Y+1)(Z+1)]
+    wr(o, M.sat);
+  } else if (mode == 0) {  // int32 seeds[n][3] -> int32 cube[n][6], queries[n]
     std::vector<int32_t> seeds(3 * (size_t)n), cube(6 * (size_t)n), q(n);
     rd(f, seeds);
     for (int i = 0; i < n; i++) q[i] = cube_of(M, &seeds[3 * i], itr, &cube[6 * i]);
@@ -116,73 +150,53 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    src = os.path.join(str(workdir), "cube_corridor_harness.cpp")
-    exe = os.path.join(str(workdir), "cube_corridor_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), cpp.compile_program(workdir, "cube_corridor_harness", HARNESS, ["-Wno-unknown-pragmas"])
 
 
-def _call(harness, grid, mode, n, arrays, cap=0, itr=1000, pop_back=1, seg_cap=0, p_max=6, f32=0, res=RES, lower=LOWER):
-    d, exe = harness
+def _call(harness, grid, mode, n, arrays, layout, cap=0, itr=1000, pop_back=1, seg_cap=0, p_max=6, f32=0, res=RES, lower=LOWER, floor=None):
+    """floor: None - the table from the map's bytes -, or (d2, min_d2) - the table through the clear header"""
     grid = np.ascontiguousarray(grid, np.uint8)
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
-    with open(fin, "wb") as f:
-        np.array(list(grid.shape) + [mode, n, cap, itr, int(pop_back), seg_cap, p_max, int(f32), 0], np.int32).tofile(f)
-        np.array([res] + list(lower), np.float64).tofile(f)
-        grid.tofile(f)
-        for a in arrays:
-            np.ascontiguousarray(a, np.int32).tofile(f)
-    subprocess.check_call([exe, fin, fout])
-    raw = open(fout, "rb").read()
-    os.remove(fout)
-    return raw
-
-
-def _take(raw, off, dt, shape):
-    n = int(np.prod(shape)) * np.dtype(dt).itemsize
-    return np.frombuffer(raw[off:off + n], dt).reshape(shape).copy(), off + n
+    field, min_d2 = ([], 0) if floor is None else ([np.ascontiguousarray(floor[0], np.int32).reshape(grid.shape)], int(floor[1]))
+    fill = FROM_MAP if floor is None else FROM_FLOOR
+    raw = cpp.exchange(harness, list(grid.shape) + [mode, n, cap, itr, int(pop_back), seg_cap, p_max, int(f32), min_d2, fill],
+                       [res] + list(lower), [grid] + field + arrays)
+    return cpp.unpack(raw, layout)
 
 
 def cubes(harness, grid, seeds, itr=1000):
     """-> (cube [n][6] lo xyz, hi xyz; queries [n])"""
     seeds = np.ascontiguousarray(seeds, np.int32).reshape(-1, 3)
     n = len(seeds)
-    raw = _call(harness, grid, 0, n, [seeds], itr=itr)
-    c, off = _take(raw, 0, np.int32, (n, 6))
-    q, off = _take(raw, off, np.int32, (n,))
-    assert off == len(raw)
-    return c, q
+    r = _call(harness, grid, CUBES, n, [seeds], (("cube", np.int32, (n, 6)), ("queries", np.int32, (n,))), itr=itr)
+    return r["cube"], r["queries"]
 
 
 def polytopes(harness, cube, res=RES, lower=LOWER):
     """-> (planes [n][6][4], center [n][3], degenerate [n])"""
     cube = np.ascontiguousarray(cube, np.int32).reshape(-1, 6)
     n = len(cube)
-    raw = _call(harness, np.zeros((1, 1, 1), np.uint8), 1, n, [cube], res=res, lower=lower)
-    p, off = _take(raw, 0, np.float64, (n, 6, 4))
-    c, off = _take(raw, off, np.float64, (n, 3))
-    d, off = _take(raw, off, np.int32, (n,))
-    assert off == len(raw)
-    return p, c, d
+    r = _call(harness, np.zeros((1, 1, 1), np.uint8), POLYTOPES, n, [cube],
+              (("planes", np.float64, (n, 6, 4)), ("center", np.float64, (n, 3)), ("degenerate", np.int32, (n,))), res=res, lower=lower)
+    return r["planes"], r["center"], r["degenerate"]
 
 
-def corridors(harness, grid, paths, path_len, res=RES, lower=LOWER, itr=1000, pop_back=True, seg_capacity=32, p_max=6, dtype=np.float64):
-    """the outputs of ClusterGenerator.cube_corridors for the same arguments, plus queries [B][path_capacity]"""
+def table(harness, grid, floor=None):
+    """-> the table in use [(X+1)][(Y+1)][(Z+1)]"""
+    return _call(harness, grid, TABLE, 0, [], (("table", np.int32, tuple(s + 1 for s in np.asarray(grid).shape)),), floor=floor)["table"]
+
+
+def corridors(harness, grid, paths, path_len, res=RES, lower=LOWER, itr=1000, pop_back=True, seg_capacity=32, p_max=6, dtype=np.float64,
+              floor=None):
+    """the outputs of ClusterGenerator.cube_corridors - with floor = (d2, min_d2) of cube_corridors_clear, without info - for the
+    same arguments, plus queries [B][path_capacity]"""
     paths = np.ascontiguousarray(paths, np.int32)
     path_len = np.ascontiguousarray(path_len, np.int32)
     B, cap = paths.shape[0], paths.shape[1]
     S, P, real = int(seg_capacity), int(p_max), np.dtype(dtype)
-    raw = _call(harness, grid, 2, B, [paths, path_len], cap=cap, itr=itr, pop_back=pop_back, seg_cap=S, p_max=P, f32=real == np.float32,
-                res=res, lower=lower)
-    out, off = {}, 0
-    for k, dt, shape in (("n_seg", np.int32, (B,)), ("n_planes", np.int32, (B, S)), ("planes", real, (B, S, P, 4)), ("seeds", real, (B, S, 3)),
-                         ("centers", real, (B, S, 3)), ("cube_idx", np.int32, (B, S, 6)), ("rtn", np.int32, (B,)), ("queries", np.int32, (B, cap))):
-        out[k], off = _take(raw, off, dt, shape)
-    assert off == len(raw)
-    return out
+    layout = (("n_seg", np.int32, (B,)), ("n_planes", np.int32, (B, S)), ("planes", real, (B, S, P, 4)), ("seeds", real, (B, S, 3)),
+              ("centers", real, (B, S, 3)), ("cube_idx", np.int32, (B, S, 6)), ("rtn", np.int32, (B,)), ("queries", np.int32, (B, cap)))
+    return _call(harness, grid, CORRIDORS, B, [paths, path_len], layout, cap=cap, itr=itr, pop_back=pop_back, seg_cap=S, p_max=P,
+                 f32=real == np.float32, res=res, lower=lower, floor=floor)
 
 
 # ---- the map and the paths the CPU and the GPU tests share ----------------------------------------------------------------

@@ -18,6 +18,7 @@ import subprocess
 import numpy as np
 
 from tests import plan_check_harness as ph
+from tests.cpp_program import compile_program
 from tests.map_cloud_harness import LOWER, RES
 
 ROOT = ph.ROOT
@@ -292,12 +293,7 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    src, exe = os.path.join(str(workdir), "dist_field_harness.cpp"), os.path.join(str(workdir), "dist_field_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), compile_program(workdir, "dist_field_harness", HARNESS)
 
 
 def run_field(harness, grid, cap_vox=0, reps=1):

@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 
 from tests import dist_field_harness as dh
+from tests.cpp_program import compile_program
 
 ROOT = dh.ROOT
 OK, NO_PATH, BAD_ENDPOINT = 0, 1, 2
@@ -376,13 +377,7 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    workdir = str(workdir)
-    src, exe = os.path.join(workdir, "free_comp_harness.cpp"), os.path.join(workdir, "free_comp_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return exe
+    return compile_program(workdir, "free_comp_harness", HARNESS)
 
 
 def run(exe, grid, d2=None, min_d2=0, cap2=0x7fffffff, order=0, starts=None, goals=None):

@@ -27,6 +27,8 @@ import subprocess
 
 import numpy as np
 
+from tests.cpp_program import compile_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, NO_PATH, BAD_ENDPOINT, OVERFLOW, ROUND_LIMIT = 0, 1, 2, 3, 4
 SIDES = ("full", "early", "emu")   # also the program's side bits and the order of its records within a query
@@ -375,14 +377,8 @@ def build_program(workdir, local_iters=None, bound_every=1):
     refreshes of a fan's bound (FAN_BOUND_EVERY; the pair sides do not look at it)"""
     assert bound_every in (1, 8)
     tag = "%s_%d" % ("lib" if local_iters is None else str(local_iters), bound_every)
-    src = os.path.join(str(workdir), "grid_path_harness.cpp")
-    exe = os.path.join(str(workdir), "grid_path_harness_" + tag)
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe, "-DFAN_BOUND_EVERY=%d" % bound_every]
-                          + ([] if local_iters is None else ["-DDIRECT_GRIDPATH_LOCAL_ITERS=%d" % local_iters]))
-    return str(workdir), exe
+    defines = ["-DFAN_BOUND_EVERY=%d" % bound_every] + ([] if local_iters is None else ["-DDIRECT_GRIDPATH_LOCAL_ITERS=%d" % local_iters])
+    return str(workdir), compile_program(workdir, "grid_path_harness", HARNESS, tail=defines, exe="grid_path_harness_" + tag)
 
 
 def build(workdir, local_iters=None):

@@ -14,6 +14,8 @@ import subprocess
 
 import numpy as np
 
+from tests.cpp_program import compile_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLAMP, DROP = 0, 1
 
@@ -178,12 +180,7 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    src, exe = os.path.join(str(workdir), "map_cloud_harness.cpp"), os.path.join(str(workdir), "map_cloud_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), compile_program(workdir, "map_cloud_harness", HARNESS)
 
 
 def run(harness, points, margin, border, dims=DIMS, res=RES, lower=LOWER, upper=UPPER, base=None, reps=1):

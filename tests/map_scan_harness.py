@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 
 from tests import map_cloud_harness as mh
+from tests.cpp_program import compile_program
 
 ROOT = mh.ROOT
 DIMS, RES, LOWER, UPPER = mh.DIMS, mh.RES, mh.LOWER, mh.UPPER   # 40 x 36 x 12 voxels of 0.15 m
@@ -213,13 +214,8 @@ int main(int argc, char** argv) {
 
 def build(workdir, sanitize=False):
     name = "map_scan_harness_san" if sanitize else "map_scan_harness"
-    src, exe = os.path.join(str(workdir), name + ".cpp"), os.path.join(str(workdir), name)
-    with open(src, "w") as f:
-        f.write(HARNESS)
     extra = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-g"] if sanitize else []
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror"] + extra +
-                          ["-I", os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), compile_program(workdir, name, HARNESS, extra)
 
 
 def run(harness, points, origin, max_range, inflate=(0, 0, 0), raw=None, before=None, dims=DIMS, res=RES, lower=LOWER, upper=UPPER,

@@ -15,6 +15,7 @@ import subprocess
 
 import numpy as np
 
+from tests.cpp_program import compile_program
 from tests.map_cloud_harness import DIMS, LOWER, RES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -326,12 +327,7 @@ int main(int argc, char** argv) {
 
 
 def build(workdir):
-    src, exe = os.path.join(str(workdir), "plan_check_harness.cpp"), os.path.join(str(workdir), "plan_check_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), compile_program(workdir, "plan_check_harness", HARNESS)
 
 
 def row_section(inp, use_t_from=True):

@@ -2,13 +2,17 @@
 runs the rounds - advance, unique, chunks, append, emit - over a table of polytopes from the CPU oracles, and the result is held
 against oracle.corridor_walk row by row, against itself under other chunk sizes and row orders, and against planted failures.
 Every row that is not planted to fail must end OK: no row is skipped or filtered."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import cluster_corridor_harness as kh
+from tests import corridor_lib as lib
 from tests import cube_corridor_harness as ch
 
 CAP = kh.CAP
+same = functools.partial(lib.same, keys=kh.KEYS)
 
 
 @pytest.fixture(scope="module")
@@ -50,11 +54,11 @@ def test_shape_independence(harness, rows):
     one = kh.corridors(harness, xyz, n, table, chunk=64)
     for chunk in (1, 2):
         got = kh.corridors(harness, xyz, n, table, chunk=chunk)
-        kh.same(got, one)
+        same(got, one)
         assert got["stats"] == one["stats"]
     perm = np.random.default_rng(1).permutation(len(rows))
     p = kh.corridors(harness, xyz[perm], n[perm], table, chunk=2)
-    kh.same(p, {k: one[k][perm] for k in kh.KEYS})
+    same(p, {k: one[k][perm] for k in kh.KEYS})
     assert p["stats"] == one["stats"]
     assert (one["rtn"] == kh.OK).all()
 
@@ -95,7 +99,7 @@ def test_planted_failure(harness, rows, how):
     for b in range(len(rows)):
         at = [s for s in range(clean["n_seg"][b]) if np.array_equal(clean["seeds"][b, s], seed)]
         if not at:
-            kh.same({k: got[k][b:b + 1] for k in kh.KEYS}, {k: clean[k][b:b + 1] for k in kh.KEYS})
+            same({k: got[k][b:b + 1] for k in kh.KEYS}, {k: clean[k][b:b + 1] for k in kh.KEYS})
             continue
         hit += 1
         k = at[0]
@@ -142,7 +146,7 @@ def test_per_row_codes(harness, rows):
     assert bad["rtn"].tolist() == case["rtn"] == [kh.BAD_PATH, kh.OK, kh.BAD_PATH, kh.BAD_PATH]
     assert bad["n_seg"][[0, 2, 3]].tolist() == [0, 0, 0] and not bad["planes"][[0, 2, 3]].any() and not bad["n_planes"][[0, 2, 3]].any()
     alone = kh.corridors(harness, bx[1:2], bn[1:2], t2, pop_back=False)
-    kh.same({k: bad[k][1:2] for k in kh.KEYS}, alone)
+    same({k: bad[k][1:2] for k in kh.KEYS}, alone)
     # path_len 0 and path_len > path_capacity
     bn2 = bn.copy()
     bn2[0], bn2[2] = 0, CAP + 1

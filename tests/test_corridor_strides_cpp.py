@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import corridor_lib as lib
 from tests import corridor_stride_lib as sl
 from tests import cube_corridor_clear_harness as cl
 from tests import cube_corridor_harness as ch
@@ -19,21 +20,17 @@ CUBE_KEYS = ("n_seg", "n_planes", "planes", "seeds", "centers", "cube_idx", "rtn
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return kh.build(tmp_path_factory.mktemp("corridor_strides_cluster"))
+    return sl.build_harness("cluster", tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def cube_harness(tmp_path_factory):
-    return ch.build(tmp_path_factory.mktemp("corridor_strides_cube"))
+    return sl.build_harness("cube", tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
 def clear_harness(tmp_path_factory):
-    return cl.build(tmp_path_factory.mktemp("corridor_strides_clear"))
-
-
-def pick(r, at, keys):
-    return {k: r[k][at] for k in keys}
+    return sl.build_harness("clear", tmp_path_factory)
 
 
 # ---- 1. polytopes over 64 planes in the walk ----------------------------------------------------------------------------------
@@ -109,7 +106,7 @@ def test_bad_voxels_behind_point_64_cluster(harness):
     mx, mn, good_at, bad_at = sl.mix_bad(rows, sl.LONG_CAP)
     got = kh.corridors(harness, mx, mn, table, seg_capacity=sl.LONG_CAP, p_max=sl.BIG_PMAX)
     sl.assert_bad_rows_empty(got, bad_at, kh.KEYS)
-    kh.same(pick(got, good_at, kh.KEYS), alone)
+    lib.same(lib.pick(got, good_at, kh.KEYS), alone, kh.KEYS)
     assert mn[bad_at].tolist() == [150, 150, 129, sl.LONG_CAP + 1]
     hx, hn = ch.pack_paths(heads, sl.LONG_CAP)
     assert hn.tolist() == [64, 100, 128] and (kh.corridors(harness, hx, hn, table, seg_capacity=sl.LONG_CAP, p_max=sl.BIG_PMAX)["rtn"] == kh.OK).all()
@@ -134,7 +131,7 @@ def test_long_paths_cube(cube_harness, pop_back):
     mx, mn, good_at, bad_at = sl.mix_bad(rows, sl.LONG_CAP)
     bad = ch.corridors(cube_harness, grid, mx, mn, pop_back=pop_back, seg_capacity=160)
     sl.assert_bad_rows_empty(bad, bad_at, CUBE_KEYS)
-    kh.same(pick(bad, good_at, CUBE_KEYS), got, CUBE_KEYS)
+    lib.same(lib.pick(bad, good_at, CUBE_KEYS), got, CUBE_KEYS)
     hx, hn = ch.pack_paths(sl.bad_row_heads(), sl.LONG_CAP)
     assert (ch.corridors(cube_harness, grid, hx, hn, pop_back=pop_back, seg_capacity=160)["rtn"] == ch.OK).all()
 
@@ -191,7 +188,7 @@ def test_big_batches(harness, pool_results, size, pop_back):
     assert len(rows) == size and 0 < (~good).sum() < size // 8
     assert (got["rtn"][good] == kh.OK).all()
     sl.assert_bad_rows_empty(got, np.flatnonzero(~good), kh.KEYS)
-    kh.same(pick(got, good, kh.KEYS), pick(alone, where[good], kh.KEYS))
+    lib.same(lib.pick(got, good, kh.KEYS), lib.pick(alone, where[good], kh.KEYS), kh.KEYS)
     prop = sl.big_properties(sl.replay_rounds(rows, table, pop_back, sl.BIG_SEG), size)
     print("%d rows, pop %d: %s, pops %d" % (size, pop_back, prop, got["stats"]["pops"]))
     s = got["stats"]

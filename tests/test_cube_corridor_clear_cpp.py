@@ -1,16 +1,20 @@
-"""direct_amd/csrc/cube_corridor_clear_math.h compiled by g++ -Wall -Werror (tests/cube_corridor_clear_harness.py), without a GPU:
+"""direct_amd/csrc/cube_corridor_clear_math.h compiled by g++ -Wall -Werror (tests/cube_corridor_harness.py, floor-filled), without a GPU:
 the floor table against NumPy, the clear call's corridors against the EXISTING harness on the thresholded map (the independent
 witness: bit for bit the plain call on (D2 < min_d2) ? 1 : 0), the integer guarantee, named cases, and the cache's slot choice.
-The map is tests/cube_corridor_harness.py's crafted map, the rows are the 40 of tests/test_gpu_cube_corridor.py."""
+The map is tests/cube_corridor_harness.py's crafted map, the rows are the 40 of tests/corridor_lib.py."""
+import functools
+
 import numpy as np
 import pytest
 
 from direct_amd import abi
+from tests import corridor_lib as lib
 from tests import cube_corridor_clear_harness as cl
 from tests import cube_corridor_harness as ch
 
 KEYS = abi.CUBE_CORRIDOR_OUTPUTS
 CAP = 40
+same = functools.partial(lib.same, keys=KEYS)
 
 
 @pytest.fixture(scope="module")
@@ -28,13 +32,8 @@ def world():
     grid = ch.crafted_map()
     d2 = cl.brute_d2(grid)
     assert int(grid.sum()) == 325 and int(d2.max()) == 146 and np.array_equal(d2 == 0, grid == 1)
-    xyz, n = ch.pack_paths(cl.rows40(), CAP)
+    xyz, n = ch.pack_paths(lib.rows40(), CAP)
     return grid, d2, xyz, n
-
-
-def same(a, b):
-    for k in KEYS:
-        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
 
 
 def seed_voxels(r):

@@ -3,24 +3,22 @@ the device, through the C-ABI: against the lock-step walk through the existing c
 oracle.corridor_walk, under other max_batch / row orders / splits, what it does to the handle and what it leaves alone, the per-row
 codes, the device-resident chain into direct_ddp_plan_batch, and the C++ mirror.  No row is skipped or filtered: every row that
 is not planted to fail must end OK, and every test asserts it."""
-import ctypes as C
-import os
-import struct
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
-from direct_amd import abi, cluster, devmem, solver
+from direct_amd import abi, cluster, solver
 from tests import cluster_corridor_harness as kh
 from tests import cluster_corridor_lib as kl
+from tests import corridor_lib as lib
 from tests import cube_corridor_harness as ch
 
 pytestmark = pytest.mark.gpu
 RES, LOWER = kh.RES, kh.LOWER
 CAP, SEG, PMAX, KEYS = kh.CAP, kh.SEG, kh.PMAX, kh.KEYS
 OK = cluster.CLUSTER_CORRIDOR_OK
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+same = functools.partial(lib.same, keys=KEYS)
 
 
 def make_gen(max_batch=64, capacity=kh.CAPACITY, grid=None):
@@ -39,10 +37,6 @@ def gen(built):
 @pytest.fixture(scope="module")
 def rows():
     return kh.inside_rows()
-
-
-def to_host(r):
-    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items()}
 
 
 def run(gen, rows, **kw):
@@ -65,18 +59,18 @@ def test_lock_step_parity(gen, rows, pop_back, itr_cluster_max):
         w = dict(want, **{k: want[k].astype(dtype) for k in ("planes", "seeds", "centers")})
         host = gen.cluster_corridors(xyz, n, LOWER, RES, itr_cluster_max=itr_cluster_max, pop_back=pop_back, seg_capacity=SEG, p_max=PMAX, dtype=dtype)
         assert (host["rtn"] == OK).all()
-        kh.same(host, w)
+        same(host, w)
         dev = gen.cluster_corridors(torch.from_numpy(xyz).to("cuda:0"), torch.from_numpy(n).to("cuda:0"), LOWER, RES, itr_cluster_max=itr_cluster_max,
                                     pop_back=pop_back, seg_capacity=SEG, p_max=PMAX, dtype=dtype)
         assert all(v.is_cuda for k, v in dev.items() if k != "stats")
-        kh.same(to_host(dev), w)
+        same(lib.to_host(dev), w)
         for s in (host["stats"], dev["stats"]):
             assert s["rounds"] == want["stats"]["rounds"] and s["due_seeds"] == want["stats"]["due_seeds"] and s["pops"] == want["stats"]["pops"]
             assert 0 < s["unique_seeds"] <= s["due_seeds"]
     if itr_cluster_max == 0:
         cube = gen.cube_corridors(xyz, n, LOWER, RES, pop_back=pop_back, seg_capacity=SEG, p_max=PMAX)
         assert (cube["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
-        kh.same(gen.cluster_corridors(xyz, n, LOWER, RES, itr_cluster_max=0, pop_back=pop_back, seg_capacity=SEG, p_max=PMAX), cube)
+        same(gen.cluster_corridors(xyz, n, LOWER, RES, itr_cluster_max=0, pop_back=pop_back, seg_capacity=SEG, p_max=PMAX), cube)
     print("cluster corridors, %d rows, pop %d, itr %d: %.3f ms, stats %s" % (len(rows), pop_back, itr_cluster_max, gen.last_ms(), host["stats"]))
 
 
@@ -99,18 +93,18 @@ def test_shape_independence(built, gen, rows):
     small = make_gen(max_batch=2)
     try:
         two = run(small, rows)
-        kh.same(two, one)
+        same(two, one)
         assert two["stats"] == one["stats"]
         perm = np.random.default_rng(1).permutation(len(rows))
         p = small.cluster_corridors(xyz[perm], n[perm], LOWER, RES, seg_capacity=SEG, p_max=PMAX)
-        kh.same(p, {k: one[k][perm] for k in KEYS})
+        same(p, {k: one[k][perm] for k in KEYS})
     finally:
         small.close()
     h = len(rows) // 2
     a = gen.cluster_corridors(xyz[:h], n[:h], LOWER, RES, seg_capacity=SEG, p_max=PMAX)
     b = gen.cluster_corridors(xyz[h:], n[h:], LOWER, RES, seg_capacity=SEG, p_max=PMAX)
-    kh.same({k: np.concatenate([a[k], b[k]]) for k in KEYS}, one)
-    kh.same(run(gen, rows), one)   # and the used workspace changes nothing
+    same({k: np.concatenate([a[k], b[k]]) for k in KEYS}, one)
+    same(run(gen, rows), one)   # and the used workspace changes nothing
     shared = kh.shared_start_rows()
     got = run(gen, shared)
     s = got["stats"]
@@ -134,9 +128,9 @@ def test_handle_state(gen, rows):
     finally:
         gen.set_map(grid)
     assert (got["rtn"] == OK).all()
-    kh.same(got, want)
+    same(got, want)
     assert got["planes"][:, :SEG, :PMAX].tobytes() != before["planes"].tobytes()
-    kh.same(run(gen, rows, itr_cluster_max=2), before)
+    same(run(gen, rows, itr_cluster_max=2), before)
     # bystanders
     seeds = np.array([[5, 5, 5], [20, 3, 3]], np.int32)
     starts, goals = np.array([[5, 5, 5], [1, 1, 1]], np.int32), np.array([[22, 18, 10], [20, 12, 5]], np.int32)
@@ -175,7 +169,7 @@ def test_per_row_codes(built, gen, rows):
         want = kl.lock_step_walk(tight, rows, LOWER, RES, False, 50, seg_capacity=SEG, p_max=PMAX)
     finally:
         tight.close()
-    kh.same(got, want)
+    same(got, want)
     codes = set(got["rtn"].tolist())
     assert codes == {OK, cluster.CLUSTER_CORRIDOR_NO_POLYTOPE}, codes
     for b in range(len(rows)):
@@ -186,7 +180,7 @@ def test_per_row_codes(built, gen, rows):
         assert (got["rtn"][b] == OK) == (k == full["n_seg"][b])
     # p_max = 8 against polytopes of up to 16 planes
     few = run(gen, rows, pop_back=False, p_max=8)
-    kh.same(few, kl.lock_step_walk(gen, rows, LOWER, RES, False, 50, seg_capacity=SEG, p_max=8))
+    same(few, kl.lock_step_walk(gen, rows, LOWER, RES, False, 50, seg_capacity=SEG, p_max=8))
     stopped = 0
     for b in range(len(rows)):
         wide = [s for s in range(full["n_seg"][b]) if full["n_planes"][b, s] > 8]
@@ -211,50 +205,30 @@ def test_per_row_codes(built, gen, rows):
     assert bad["rtn"].tolist() == [OK, B, OK, B, B, B]
     for b in (1, 3, 4, 5):
         assert bad["n_seg"][b] == 0 and not any(bad[k][b].any() for k in ("n_planes", "planes", "seeds", "centers"))
-    kh.same({k: bad[k][[0, 2]] for k in KEYS}, {k: full[k][[0, 1]] for k in KEYS})
+    same({k: bad[k][[0, 2]] for k in KEYS}, {k: full[k][[0, 1]] for k in KEYS})
 
 
 def test_abi_edges(gen, rows):
     """5b.  every DIRECT_ERR_INVALID case of the header launches nothing (the outputs keep their bytes); NULL outputs are left alone"""
     L = cluster._lib()
     xyz, n = ch.pack_paths(rows[:4], CAP)
-    out = {k: np.full(s, 77, d) for k, s, d in (("n_seg", 4, np.int32), ("n_planes", (4, SEG), np.int32), ("planes", (4, SEG, PMAX, 4), np.float64),
-                                                ("seeds", (4, SEG, 3), np.float64), ("centers", (4, SEG, 3), np.float64), ("rtn", 4, np.int32))}
-    keep = {k: v.copy() for k, v in out.items()}
     stats = np.full(4, -5, np.int64)
 
-    def call(h=None, null_in=False, null_out=False, omem=abi.MEM_HOST, **kw):
-        par = cluster.ClusterCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                        path_len=n.ctypes.data, itr_cluster_max=2, pop_back=1, seg_capacity=SEG, p_max=PMAX, plane_dtype=abi.F64,
-                                        resolution=RES, map_lower=(C.c_double * 3)(*LOWER))
-        for k, v in kw.items():
-            setattr(par, k, v)
-        o = cluster.ClusterCorridorOut(omem, 0, *[out[k].ctypes.data for k in KEYS])
-        return L.direct_cluster_corridor_batch(gen.h if h is None else h, None if null_in else C.addressof(par),
-                                               None if null_out else C.addressof(o), stats.ctypes.data)
+    def entry(h, par, o, stats=stats.ctypes.data):
+        return L.direct_cluster_corridor_batch(h, par, o, stats)
 
-    nan, inf = float("nan"), float("inf")
-    invalid = [dict(h=C.c_void_p(None)), dict(null_in=True), dict(null_out=True), dict(path_xyz=None), dict(path_len=None), dict(batch=0),
-               dict(batch=-1), dict(path_capacity=0), dict(seg_capacity=0), dict(itr_inflate_max=0), dict(itr_cluster_max=-1), dict(p_max=5),
-               dict(mem_in=2), dict(omem=2), dict(plane_dtype=2), dict(resolution=0.0), dict(resolution=-0.2), dict(resolution=nan),
-               dict(resolution=inf), dict(map_lower=(C.c_double * 3)(0.0, nan, 0.0))]
-    for kw in invalid:
-        assert call(**kw) == abi.DIRECT_ERR_INVALID, kw
-        assert all(out[k].tobytes() == keep[k].tobytes() for k in KEYS) and (stats == -5).all(), kw
-    fresh = cluster.ClusterGenerator(ch.DIMS, max_batch=4, cluster_capacity=64, candidate_capacity=64)   # a handle without a map
-    try:
-        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID
-    finally:
-        fresh.close()
-    assert all(out[k].tobytes() == keep[k].tobytes() for k in KEYS)
-    assert call(batch=1 << 20, path_capacity=1 << 8) == abi.DIRECT_ERR_UNSUPPORTED
-    assert call() == abi.DIRECT_OK and (out["rtn"] == OK).all() and stats[0] > 0
-    only = np.full(4, -1, np.int32)
-    par = cluster.ClusterCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                    path_len=n.ctypes.data, itr_cluster_max=2, pop_back=1, seg_capacity=SEG, p_max=PMAX, plane_dtype=abi.F64,
-                                    resolution=RES, map_lower=(C.c_double * 3)(*LOWER))
-    o = cluster.ClusterCorridorOut(abi.MEM_HOST, 0, None, None, None, None, None, only.ctypes.data)
-    assert L.direct_cluster_corridor_batch(gen.h, C.addressof(par), C.addressof(o), None) == abi.DIRECT_OK and not only.any()
+    raw = lib.RawCall(gen, entry, cluster.ClusterCorridorIn, cluster.ClusterCorridorOut, KEYS, xyz, n, SEG, PMAX, extras=(stats,),
+                      itr_cluster_max=2)
+    for kw in lib.INVALID + [dict(itr_cluster_max=-1)]:
+        assert raw.call(**kw) == abi.DIRECT_ERR_INVALID, kw
+        assert raw.untouched() and (stats == -5).all(), kw
+    with lib.handle_without_map() as fresh:
+        assert raw.call(h=fresh.h) == abi.DIRECT_ERR_INVALID
+    assert raw.untouched()
+    assert raw.call(batch=1 << 20, path_capacity=1 << 8) == abi.DIRECT_ERR_UNSUPPORTED
+    assert raw.call() == abi.DIRECT_OK and (raw.out["rtn"] == OK).all() and stats[0] > 0
+    status, only = raw.only_codes(stats=None)
+    assert status == abi.DIRECT_OK and not only.any()
 
 
 def test_chain_on_the_device_into_the_optimiser(built):
@@ -274,37 +248,14 @@ def test_chain_on_the_device_into_the_optimiser(built):
     hcor = gen.cluster_corridors(hx, hn, LOWER, RES, itr_cluster_max=50, seg_capacity=N, p_max=P)
     gen.close()
     assert (hp["rtn"] == cluster.GRID_PATH_OK).all() and (hcor["rtn"] == OK).all()
-    kh.same(to_host(cor), hcor)
-    centre = lambda v: v.to(torch.float64) * RES + 0.5 * RES + torch.from_numpy(LOWER).to(dev)
-    rowsel = torch.arange(B, device=dev)
-    last = (paths["path_len"] - 1).long()
-    x0, xd = torch.zeros((B, 9), dtype=torch.float64, device=dev), torch.zeros((B, 9), dtype=torch.float64, device=dev)
-    x0[:, :3] = centre(paths["path_xyz"][rowsel, 0])
-    xd[:, :3] = centre(paths["path_xyz"][rowsel, last])
-    t = dict(n_seg=cor["n_seg"], x0=x0, xd=xd, n_planes=cor["n_planes"], planes=cor["planes"], seeds=cor["seeds"])
-    cin = abi.BatchIn()
-    cin.batch, cin.n_seg_max, cin.p_max, cin.mem = B, N, P, abi.MEM_DEVICE
-    for k, v in t.items():
-        setattr(cin, k, v.data_ptr())
-    p0, p1 = abi.phase0_params(iter_max=20), abi.phase1_params(iter_max=20)
-    s = solver.DdpSolver(B, N, P, np.float64, device=0)
-    o0, o1 = devmem.DeviceResult(B, N, np.float64, dev), devmem.DeviceResult(B, N, np.float64, dev)
-    torch.cuda.synchronize()
-    s.plan_device(p0, p1, cin, o0.cout, o1.cout)
-    torch.cuda.synchronize()
-    hx0 = np.zeros((B, 9))
-    hxd = np.zeros((B, 9))
+    same(lib.to_host(cor), hcor)
+    x0, xd = lib.chain_ends(paths, torch.arange(B, device=dev))
+    hx0, hxd = np.zeros((B, 9)), np.zeros((B, 9))
     hx0[:, :3] = starts * RES + 0.5 * RES + LOWER
     hxd[:, :3] = goals * RES + 0.5 * RES + LOWER
-    assert np.array_equal(hx0, x0.cpu().numpy()) and np.array_equal(hxd, xd.cpu().numpy())
-    hb = abi.HostBatch(hcor["n_seg"], hx0, hxd, np.zeros((B, N)), hcor["n_planes"], hcor["planes"], seeds=hcor["seeds"]).without_T0()
-    r0, r1 = s.plan(p0, p1, hb)
-    s.close()
-    d0, d1 = o0.to_host(), o1.to_host()
+    assert np.array_equal(hx0, x0.cpu().numpy()) and np.array_equal(hxd, xd.cpu().numpy())   # so the host copies are the host chain's
+    _, (r0, r1), (_, d1) = lib.plan_chain(cor, x0, xd, N, P)
     print("chain: %d rows, n_seg %s, rtn %s, stats %s" % (B, hcor["n_seg"].tolist(), r1.rtn.tolist(), hcor["stats"]))
-    for dv, hv in ((d0, r0), (d1, r1)):
-        for k in ("rtn", "iter_used", "fwd_passes", "cost", "T", "bez", "poly"):
-            assert np.asarray(getattr(dv, k)).tobytes() == np.asarray(getattr(hv, k)).tobytes(), k
     assert (np.asarray(r0.rtn) != abi.RTN_INVALID).all() and (np.asarray(r1.rtn) != abi.RTN_INVALID).all()
     assert (np.asarray(d1.rtn) != abi.RTN_INVALID).all()
 
@@ -313,16 +264,4 @@ def test_chain_on_the_device_into_the_optimiser(built):
 def test_cpp_mirror_against_its_lock_step_walks(built, rows, tmp_path, itr_cluster_max):
     """7.  polyhedronGenerator::clusterCorridorBatch (direct_amd/host/poly_utils.hpp) gives the corridors of corridorGenerationBatch /
     corridorInsertGenerationBatch from empty corridors, bit for bit (tests/cpp/test_cluster_corridor_gen.cpp)"""
-    fin, exe = str(tmp_path / "in.bin"), str(tmp_path / "gen")
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<3id3di", *ch.DIMS, RES, *LOWER, len(rows)))
-        for p in rows:
-            f.write(struct.pack("<i", len(p)))
-            f.write(np.ascontiguousarray(p.astype(np.float64) * RES + 0.5 * RES + LOWER, np.float64).tobytes())
-        f.write(ch.crafted_map().tobytes())
-    lib = os.path.dirname(solver.LIB_PATH)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests/cpp/test_cluster_corridor_gen.cpp"), "-o", exe,
-                           "-L" + lib, "-ldirect_ddp", "-Wl,-rpath," + lib + ":/opt/rocm/lib"])
-    out = subprocess.run([exe, fin, str(itr_cluster_max), str(kh.CAPACITY)], capture_output=True, text=True)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    lib.run_cpp_mirror(tmp_path, "test_cluster_corridor_gen.cpp", rows, args=(itr_cluster_max, kh.CAPACITY))

@@ -11,6 +11,7 @@ import pytest
 
 from direct_amd import abi, cluster
 from tests import cluster_corridor_harness as kh
+from tests import corridor_lib as lib
 from tests import corridor_stride_lib as sl
 from tests import cube_corridor_clear_harness as cl
 from tests import cube_corridor_harness as ch
@@ -23,17 +24,17 @@ DEV = "cuda:0"
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return kh.build(tmp_path_factory.mktemp("corridor_strides_gpu_cluster"))
+    return sl.build_harness("cluster", tmp_path_factory, "gpu_")
 
 
 @pytest.fixture(scope="module")
 def cube_harness(tmp_path_factory):
-    return ch.build(tmp_path_factory.mktemp("corridor_strides_gpu_cube"))
+    return sl.build_harness("cube", tmp_path_factory, "gpu_")
 
 
 @pytest.fixture(scope="module")
 def clear_harness(tmp_path_factory):
-    return cl.build(tmp_path_factory.mktemp("corridor_strides_gpu_clear"))
+    return sl.build_harness("clear", tmp_path_factory, "gpu_")
 
 
 def make_gen(grid, max_batch=64):
@@ -69,10 +70,6 @@ def gen_cube(built):
 def on_device(xyz, n):
     import torch
     return torch.from_numpy(xyz).to(DEV), torch.from_numpy(n).to(DEV)
-
-
-def pick(r, at, keys):
-    return {k: r[k][at] for k in keys}
 
 
 def dirty_call(gen, keys, xyz, n, dtype, pop_back, seg_capacity, p_max=6, itr_cluster_max=None, min_d2=None):
@@ -119,7 +116,7 @@ def cluster_both(gen, harness, xyz, n, table, cases, **kw):
             got = dirty_call(gen, KEYS, xyz, n, dtype, itr_cluster_max=sl.BIG_ITR, **kw)
         else:
             got = gen.cluster_corridors(xyz, n, LOWER, RES, itr_cluster_max=sl.BIG_ITR, dtype=dtype, **kw)
-        kh.same(got, want)
+        lib.same(got, want, KEYS)
         assert got["stats"] == want["stats"], (got["stats"], want["stats"])
         first = got if first is None else first
     return first
@@ -148,7 +145,7 @@ def test_polytopes_over_64_planes_in_the_walk(built, gen_balls, harness, pop_bac
         two = cluster_both(small, harness, xyz, n, table, ((np.float64, False),), **kw)
     finally:
         small.close()
-    kh.same(two, got)
+    lib.same(two, got, KEYS)
     print("wide polytopes, %d rows, pop %d: %.3f ms, max planes %d, stats %s" % (len(rows), pop_back, ms, got["n_planes"].max(), got["stats"]))
 
 
@@ -197,7 +194,7 @@ def test_bad_voxels_behind_point_64_cluster(gen_crafted, harness):
     got = cluster_both(gen_crafted, harness, mx, mn, table, TWO_CASES, **kw)
     sl.assert_bad_rows_empty(got, bad_at, KEYS)
     assert (got["rtn"][good_at] == kh.OK).all()
-    kh.same(pick(got, good_at, KEYS), alone)
+    lib.same(lib.pick(got, good_at, KEYS), alone, KEYS)
 
 
 def cube_both(gen, cube_harness, grid, xyz, n, cases, **kw):
@@ -205,7 +202,7 @@ def cube_both(gen, cube_harness, grid, xyz, n, cases, **kw):
     for dtype, dev in cases:
         want = ch.corridors(cube_harness, grid, xyz, n, dtype=dtype, **kw)
         got = dirty_call(gen, CUBE_KEYS, xyz, n, dtype, **kw) if dev else gen.cube_corridors(xyz, n, LOWER, RES, dtype=dtype, **kw)
-        kh.same(got, want, CUBE_KEYS)
+        lib.same(got, want, CUBE_KEYS)
         first = got if first is None else first
     return first
 
@@ -227,7 +224,7 @@ def test_long_paths_cube(gen_cube, cube_harness, pop_back):
     mx, mn, good_at, bad_at = sl.mix_bad(rows, sl.LONG_CAP)
     bad = cube_both(gen_cube, cube_harness, grid, mx, mn, TWO_CASES, pop_back=pop_back, seg_capacity=160)
     sl.assert_bad_rows_empty(bad, bad_at, CUBE_KEYS)
-    kh.same(pick(bad, good_at, CUBE_KEYS), got, CUBE_KEYS)
+    lib.same(lib.pick(bad, good_at, CUBE_KEYS), got, CUBE_KEYS)
     print("long paths, cube, pop %d: %.3f ms, n_seg up to %d" % (pop_back, ms, got["n_seg"].max()))
 
 
@@ -244,7 +241,7 @@ def test_long_paths_clear(gen_cube, clear_harness):
             got = dirty_call(gen_cube, CUBE_KEYS, xyz, n, dtype, pop_back, 160, min_d2=sl.CLEAR_FLOOR)
         else:
             got = gen_cube.cube_corridors_clear(xyz, n, LOWER, RES, sl.CLEAR_FLOOR, pop_back=pop_back, seg_capacity=160, dtype=dtype)
-        kh.same(got, want, CUBE_KEYS)
+        lib.same(got, want, CUBE_KEYS)
         assert (got["rtn"] == ch.OK).all() and got["n_seg"].max() > 64
         print("long paths, floor %d, pop %d: %.3f ms, n_seg up to %d" % (sl.CLEAR_FLOOR, pop_back, gen_cube.last_ms(), got["n_seg"].max()))
 
@@ -278,24 +275,24 @@ def test_big_batch_shape_independence(built, gen_crafted, harness, big_tables):
     xyz, n = ch.pack_paths(sl.big_batch(2500), sl.BIG_CAP)
     run = lambda g, a, b: g.cluster_corridors(a, b, LOWER, RES, itr_cluster_max=sl.BIG_ITR, pop_back=True, **BIG_KW)
     one = run(gen_crafted, xyz, n)
-    kh.same(one, kh.corridors(harness, xyz, n, big_tables[True], pop_back=True, **BIG_KW))
+    lib.same(one, kh.corridors(harness, xyz, n, big_tables[True], pop_back=True, **BIG_KW), KEYS)
     small = make_gen(ch.crafted_map(), max_batch=2)
     try:
         two = run(small, xyz, n)
         ms = small.last_ms()
     finally:
         small.close()
-    kh.same(two, one)
+    lib.same(two, one, KEYS)
     assert two["stats"] == one["stats"]
     perm = np.random.default_rng(1).permutation(len(n))
     assert (perm[:1024] >= 1024).any() and (perm[1024:] < 1024).any()
     p = run(gen_crafted, xyz[perm], n[perm])
-    kh.same(p, pick(one, perm, KEYS))
+    lib.same(p, lib.pick(one, perm, KEYS), KEYS)
     assert {k: v for k, v in p["stats"].items()} == one["stats"]
     four = run(gen_crafted, xyz[:4], n[:4])
-    kh.same(four, pick(one, slice(0, 4), KEYS))
+    lib.same(four, lib.pick(one, slice(0, 4), KEYS), KEYS)
     again = run(gen_crafted, xyz, n)
-    kh.same(again, one)
+    lib.same(again, one, KEYS)
     assert again["stats"] == one["stats"]
     print("2500 rows: %.3f ms at max_batch 64, %.3f ms at max_batch 2, stats %s" % (gen_crafted.last_ms(), ms, one["stats"]))
 

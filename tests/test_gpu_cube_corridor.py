@@ -3,28 +3,20 @@ the device, through the C-ABI: against the g++ build of the same arithmetic (tes
 three independent witnesses by tests/test_cube_corridor_restatement.py), against the path that exists beside it - a lock-step walk
 over polygon_generation(seed, itr, 0) + hull_planes() on the same handle -, launch-shape independence, a change of map, what the
 call leaves alone, the device-resident chain into direct_ddp_plan_batch, and the edges of the ABI."""
-import ctypes as C
-import os
-import struct
-import subprocess
+import functools
 
 import numpy as np
 import pytest
 
-from direct_amd import abi, cluster, devmem, solver
+from direct_amd import abi, cluster
+from tests import corridor_lib as lib
 from tests import cube_corridor_harness as ch
 
 pytestmark = pytest.mark.gpu
 RES, LOWER = ch.RES, ch.LOWER
 KEYS = abi.CUBE_CORRIDOR_OUTPUTS
 CAP, SEG = 40, 32
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def same(a, b, keys=KEYS):
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), k
+same = functools.partial(lib.same, keys=KEYS)
 
 
 @pytest.fixture(scope="module")
@@ -42,18 +34,7 @@ def gen(built):
 
 @pytest.fixture(scope="module")
 def rows():
-    """the paths of the named cases that lie inside the map, and random walks: 40 rows on the crafted map"""
-    paths = []
-    for c in ch.named_cases():
-        if c["name"] != "outside_voxel":
-            paths += [p for p in c["paths"]]
-    paths += ch.random_paths(ch.crafted_map(), 40 - len(paths), seed=9)
-    assert len(paths) == 40
-    return [np.asarray(p, np.int32) for p in paths]
-
-
-def to_host(r):
-    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in r.items()}
+    return lib.rows40()
 
 
 def test_device_equals_the_harness(gen, harness, rows):
@@ -70,7 +51,7 @@ def test_device_equals_the_harness(gen, harness, rows):
         dev = gen.cube_corridors(torch.from_numpy(xyz).to("cuda:0"), torch.from_numpy(n).to("cuda:0"), LOWER, res, pop_back=pop_back,
                                  seg_capacity=SEG, p_max=7, dtype=dtype)
         assert all(v.is_cuda for v in dev.values())
-        same(to_host(dev), want)
+        same(lib.to_host(dev), want)
         assert want["rtn"][:len(rows)].tolist() == [ch.OK] * len(rows) and (want["rtn"][len(rows):] == ch.BAD_PATH).sum() == 3
     print("cube corridors of %d rows: %.3f ms, up to %d polytopes per row" % (len(n), gen.last_ms(), want["n_seg"].max()))
 
@@ -162,33 +143,12 @@ def test_follows_the_map_the_handle_holds(gen, harness, rows):
 
 def test_leaves_the_rest_of_the_handle_alone(gen, rows):
     """5.  resident clusters, a grid-path result and the distance field from before the call are unchanged by it"""
-    grid = ch.crafted_map()
     xyz, n = ch.pack_paths(rows, CAP)
-    seeds = np.array([[5, 5, 5], [20, 3, 3], [13, 4, 4], [15, 12, 5]], np.int32)
-    starts, goals = np.array([[5, 5, 5], [1, 1, 1]], np.int32), np.array([[22, 18, 10], [20, 12, 5]], np.int32)
-    gen.polygon_generation(seeds, 1000, 0, fetch_clusters=False)
-    want_hull = gen.hull_planes(RES, LOWER, batch=len(seeds), plane_capacity=64, vertex_capacity=64)
-    want_path = gen.grid_paths(starts, goals, path_capacity=64, want_dist=True)
-    dev_path = gen.grid_paths(starts, goals, path_capacity=64, mem="device")
-    keep = {k: v.clone() for k, v in dev_path.items()}
     gen.build_distance_field()
-    want_field = gen.distance_field()
-    gen.polygon_generation(seeds, 1000, 0, fetch_clusters=False)
+    by = lib.Bystanders(gen)
     gen.cube_corridors(xyz, n, LOWER, RES, seg_capacity=SEG)
-    gen.cube_corridors(dev_path["path_xyz"], dev_path["path_len"], LOWER, RES, seg_capacity=SEG)
-    got_hull = gen.hull_planes(RES, LOWER, batch=len(seeds), plane_capacity=64, vertex_capacity=64)
-    assert np.array_equal(gen.distance_field(), want_field)   # still valid, still the same
-    assert (want_hull["rtn"] == cluster.HULL_OK).all()
-    for k in ("rtn", "n_planes", "n_vertices", "degenerate", "center"):
-        assert np.array_equal(want_hull[k], got_hull[k]), k
-    for b in range(len(seeds)):
-        assert np.array_equal(want_hull["planes"][b], got_hull["planes"][b]) and np.array_equal(want_hull["vertices"][b], got_hull["vertices"][b])
-    for k, v in dev_path.items():
-        assert v.cpu().numpy().tobytes() == keep[k].cpu().numpy().tobytes(), k
-    again = gen.grid_paths(starts, goals, path_capacity=64, want_dist=True)
-    assert (want_path["rtn"] == cluster.GRID_PATH_OK).all() and np.array_equal(again["path_len"], want_path["path_len"])
-    assert all(np.array_equal(a, b) for a, b in zip(again["paths"], want_path["paths"]))
-    assert np.array_equal(grid, gen.get_map())
+    gen.cube_corridors(by.dev_path["path_xyz"], by.dev_path["path_len"], LOWER, RES, seg_capacity=SEG)
+    by.check()
 
 
 def test_chain_on_the_device_into_the_optimiser(built):
@@ -212,75 +172,27 @@ def test_chain_on_the_device_into_the_optimiser(built):
     pick = torch.nonzero(ok).flatten()[:6]
     B = int(pick.numel())
     assert B >= 2, (cor["rtn"].cpu(), cor["n_seg"].cpu(), paths["rtn"].cpu())
-    centre = lambda v: v.to(torch.float64) * RES + 0.5 * RES + torch.from_numpy(LOWER).to(dev)
-    last = (paths["path_len"][pick] - 1).long()
-    x0, xd = torch.zeros((B, 9), dtype=torch.float64, device=dev), torch.zeros((B, 9), dtype=torch.float64, device=dev)
-    x0[:, :3] = centre(paths["path_xyz"][pick, 0])
-    xd[:, :3] = centre(paths["path_xyz"][pick, last])
-    t = dict(n_seg=cor["n_seg"][pick].contiguous(), x0=x0, xd=xd, n_planes=cor["n_planes"][pick].contiguous(),
-             planes=cor["planes"][pick].contiguous(), seeds=cor["seeds"][pick].contiguous())
-    cin = abi.BatchIn()
-    cin.batch, cin.n_seg_max, cin.p_max, cin.mem = B, N, P, abi.MEM_DEVICE
-    for k, v in t.items():
-        setattr(cin, k, v.data_ptr())
-    p0, p1 = abi.phase0_params(iter_max=20), abi.phase1_params(iter_max=20)
-    s = solver.DdpSolver(B, N, P, np.float64, device=0)
-    o0, o1 = devmem.DeviceResult(B, N, np.float64, dev), devmem.DeviceResult(B, N, np.float64, dev)
-    torch.cuda.synchronize()
-    s.plan_device(p0, p1, cin, o0.cout, o1.cout)
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in t.items()}
-    hb = abi.HostBatch(h["n_seg"], h["x0"], h["xd"], np.zeros((B, N)), h["n_planes"], h["planes"], seeds=h["seeds"]).without_T0()
-    r0, r1 = s.plan(p0, p1, hb)
-    s.close()
-    d0, d1 = o0.to_host(), o1.to_host()
+    x0, xd = lib.chain_ends(paths, pick)
+    h, (_, r1), _ = lib.plan_chain({k: cor[k][pick] for k in ("n_seg", "n_planes", "planes", "seeds")}, x0, xd, N, P)
     print("chain: %d rows, n_seg %s, rtn %s" % (B, h["n_seg"].tolist(), r1.rtn.tolist()))
-    for dv, hv in ((d0, r0), (d1, r1)):
-        for k in ("rtn", "iter_used", "fwd_passes", "cost", "T", "bez", "poly"):
-            assert np.asarray(getattr(dv, k)).tobytes() == np.asarray(getattr(hv, k)).tobytes(), k
     assert (h["n_seg"] <= N).all()
 
 
 def test_abi_edges(gen, rows):
     """7.  every DIRECT_ERR_INVALID case launches nothing (the outputs keep their bytes); OVERFLOW and BAD_PATH rows beside good ones"""
-    L = cluster._lib()
     xyz, n = ch.pack_paths(rows[:4], CAP)
-    out = {k: np.full(s, 77, d) for k, s, d in (("n_seg", 4, np.int32), ("n_planes", (4, SEG), np.int32), ("planes", (4, SEG, 6, 4), np.float64),
-                                                ("seeds", (4, SEG, 3), np.float64), ("centers", (4, SEG, 3), np.float64),
-                                                ("cube_idx", (4, SEG, 6), np.int32), ("rtn", 4, np.int32))}
-    keep = {k: v.copy() for k, v in out.items()}
-
-    def call(h=None, null_in=False, null_out=False, omem=abi.MEM_HOST, **kw):
-        par = cluster.CubeCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                     path_len=n.ctypes.data, pop_back=1, seg_capacity=SEG, p_max=6, plane_dtype=abi.F64, resolution=RES,
-                                     map_lower=(C.c_double * 3)(*LOWER))
-        for k, v in kw.items():
-            setattr(par, k, v)
-        o = cluster.CubeCorridorOut(omem, 0, *[out[k].ctypes.data for k in KEYS])
-        return L.direct_cluster_cube_corridor_batch(gen.h if h is None else h, None if null_in else C.addressof(par),
-                                                    None if null_out else C.addressof(o))
-
-    nan, inf = float("nan"), float("inf")
-    invalid = [dict(h=C.c_void_p(None)), dict(null_in=True), dict(null_out=True), dict(path_xyz=None), dict(path_len=None), dict(batch=0),
-               dict(batch=-1), dict(path_capacity=0), dict(seg_capacity=0), dict(itr_inflate_max=0), dict(p_max=5), dict(mem_in=2),
-               dict(omem=2), dict(plane_dtype=2), dict(resolution=0.0), dict(resolution=-0.2), dict(resolution=nan), dict(resolution=inf)]
-    for kw in invalid:
-        assert call(**kw) == abi.DIRECT_ERR_INVALID, kw
-        assert all(out[k].tobytes() == keep[k].tobytes() for k in KEYS), kw
-    fresh = cluster.ClusterGenerator(ch.DIMS, max_batch=4, cluster_capacity=64, candidate_capacity=64)   # a handle without a map
-    try:
-        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID
-    finally:
-        fresh.close()
-    assert all(out[k].tobytes() == keep[k].tobytes() for k in KEYS)
-    assert call() == abi.DIRECT_OK and (out["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
+    raw = lib.RawCall(gen, cluster._lib().direct_cluster_cube_corridor_batch, cluster.CubeCorridorIn, cluster.CubeCorridorOut, KEYS, xyz, n,
+                      SEG, 6)
+    for kw in lib.INVALID:
+        assert raw.call(**kw) == abi.DIRECT_ERR_INVALID, kw
+        assert raw.untouched(), kw
+    with lib.handle_without_map() as fresh:
+        assert raw.call(h=fresh.h) == abi.DIRECT_ERR_INVALID
+    assert raw.untouched()
+    assert raw.call() == abi.DIRECT_OK and (raw.out["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
     # NULL outputs are left alone: only the codes
-    only = np.full(4, -1, np.int32)
-    par = cluster.CubeCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                 path_len=n.ctypes.data, pop_back=1, seg_capacity=SEG, p_max=6, plane_dtype=abi.F64, resolution=RES,
-                                 map_lower=(C.c_double * 3)(*LOWER))
-    o = cluster.CubeCorridorOut(abi.MEM_HOST, 0, None, None, None, None, None, None, only.ctypes.data)
-    assert L.direct_cluster_cube_corridor_batch(gen.h, C.addressof(par), C.addressof(o)) == abi.DIRECT_OK and not only.any()
+    status, only = raw.only_codes()
+    assert status == abi.DIRECT_OK and not only.any()
     # per-row codes beside good rows
     uturn = next(c for c in ch.named_cases() if c["name"] == "u_turn_no_pop")["paths"][0]
     mixed = [rows[0], uturn, [[24, 0, 0]], rows[1], np.zeros((0, 3), np.int32), uturn]
@@ -302,16 +214,4 @@ def test_abi_edges(gen, rows):
 def test_cpp_mirror_against_its_lock_step_walks(gen, rows, tmp_path):
     """8.  polyhedronGenerator::cubeCorridorBatch (direct_amd/host/poly_utils.hpp) gives the corridors of corridorGenerationBatch /
     corridorInsertGenerationBatch on a generator without clustering, bit for bit (tests/cpp/test_cube_corridor_gen.cpp)"""
-    fin, exe = str(tmp_path / "in.bin"), str(tmp_path / "gen")
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<3id3di", *ch.DIMS, RES, *LOWER, len(rows)))
-        for p in rows:
-            f.write(struct.pack("<i", len(p)))
-            f.write(np.ascontiguousarray(p.astype(np.float64) * RES + 0.5 * RES + LOWER, np.float64).tobytes())
-        f.write(ch.crafted_map().tobytes())
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests/cpp/test_cube_corridor_gen.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "direct_amd/lib"), "-ldirect_ddp",
-                           "-Wl,-rpath," + os.path.join(ROOT, "direct_amd/lib") + ":/opt/rocm/lib"])
-    out = subprocess.run([exe, fin], capture_output=True, text=True)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    lib.run_cpp_mirror(tmp_path, "test_cube_corridor_gen.cpp", rows)

@@ -1,17 +1,16 @@
 """direct_cluster_cube_corridor_clear_batch (include/direct_cluster.h, "radius-aware cube corridors"; k_floor_fill in
 direct_amd/csrc/cube_corridor_clear.h) on the device, through the C-ABI: against the g++ build of the same arithmetic
-(tests/cube_corridor_clear_harness.py), against the independent witness - the PLAIN call on a second handle that holds the
+(tests/cube_corridor_clear_harness.py on the program of tests/cube_corridor_harness.py), against the independent witness - the PLAIN call on a second handle that holds the
 thresholded field as its map -, neutral mode, the refusals, the cache of floor tables, launch-shape independence, what the call
 leaves alone, the device-resident chain into direct_ddp_plan_batch, and the C++ mirror."""
-import ctypes as C
-import os
+import functools
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-from direct_amd import abi, cluster, devmem, solver
+from direct_amd import abi, cluster, solver
+from tests import corridor_lib as lib
 from tests import cube_corridor_clear_harness as cl
 from tests import cube_corridor_harness as ch
 
@@ -20,17 +19,7 @@ RES, LOWER = ch.RES, ch.LOWER
 KEYS = abi.CUBE_CORRIDOR_OUTPUTS
 CAP, SEG = 40, 40
 BELOW = {4: 1243, 9: 2523, 16: 3669}   # (d2 < floor).sum() on the crafted map
-ROOT = ch.ROOT
-
-
-def same(a, b, keys=KEYS):
-    for k in keys:
-        x, y = np.asarray(a[k]), np.asarray(b[k])
-        assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), k
-
-
-def to_host(r):
-    return {k: (v if isinstance(v, np.ndarray) else v.cpu().numpy()) for k, v in r.items()}
+same = functools.partial(lib.same, keys=KEYS)
 
 
 @pytest.fixture(scope="module")
@@ -59,7 +48,7 @@ def d2(gen):
 
 @pytest.fixture(scope="module")
 def rows():
-    return cl.rows40()
+    return lib.rows40()
 
 
 def test_device_equals_the_clear_harness(gen, harness, rows, d2):
@@ -77,7 +66,7 @@ def test_device_equals_the_clear_harness(gen, harness, rows, d2):
             same(host, want)
             dev = gen.cube_corridors_clear(txyz, tn, LOWER, RES, floor, pop_back=pop_back, seg_capacity=SEG, p_max=7, dtype=dtype)
             assert all(dev[k].is_cuda for k in KEYS) and isinstance(dev["info"], np.ndarray)
-            same(to_host(dev), want)
+            same(lib.to_host(dev), want)
             assert want["rtn"][:len(rows)].tolist() == [ch.OK] * len(rows) and (want["rtn"][len(rows):] == ch.BAD_PATH).sum() == 3
             assert host["info"][1] == dev["info"][1] == (d2 < floor).sum()
         print("floor %d: %.3f ms, %d polytopes, up to %d per row" % (floor, gen.last_ms(), want["n_seg"].sum(), want["n_seg"].max()))
@@ -126,60 +115,37 @@ def test_refusals(gen, rows):
     floor AT the cap succeeds and equals the uncapped field's result), a negative floor, and what the plain call refuses"""
     L = cluster._lib()
     xyz, n = ch.pack_paths(rows[:4], CAP)
-    out = {k: np.full(s, 77, d) for k, s, d in (("n_seg", 4, np.int32), ("n_planes", (4, SEG), np.int32), ("planes", (4, SEG, 6, 4), np.float64),
-                                                ("seeds", (4, SEG, 3), np.float64), ("centers", (4, SEG, 3), np.float64),
-                                                ("cube_idx", (4, SEG, 6), np.int32), ("rtn", 4, np.int32))}
-    keep = {k: v.copy() for k, v in out.items()}
     info = np.full(2, 77, np.int64)
 
-    def call(h=None, min_d2=4, null_in=False, null_out=False, omem=abi.MEM_HOST, **kw):
-        par = cluster.CubeCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                     path_len=n.ctypes.data, pop_back=1, seg_capacity=SEG, p_max=6, plane_dtype=abi.F64, resolution=RES,
-                                     map_lower=(C.c_double * 3)(*LOWER))
-        for k, v in kw.items():
-            setattr(par, k, v)
-        o = cluster.CubeCorridorOut(omem, 0, *[out[k].ctypes.data for k in KEYS])
-        return L.direct_cluster_cube_corridor_clear_batch(gen.h if h is None else h, None if null_in else C.addressof(par), min_d2,
-                                                          None if null_out else C.addressof(o), info.ctypes.data)
+    def entry(h, par, o, min_d2=4, info=info.ctypes.data):
+        return L.direct_cluster_cube_corridor_clear_batch(h, par, min_d2, o, info)
 
-    def untouched():
-        return all(out[k].tobytes() == keep[k].tobytes() for k in KEYS) and info.tolist() == [77, 77]
-
-    nan, inf = float("nan"), float("inf")
-    invalid = [dict(min_d2=-1), dict(min_d2=-2 ** 31), dict(h=C.c_void_p(None)), dict(null_in=True), dict(null_out=True), dict(path_xyz=None),
-               dict(path_len=None), dict(batch=0), dict(batch=-1), dict(path_capacity=0), dict(seg_capacity=0), dict(itr_inflate_max=0),
-               dict(p_max=5), dict(mem_in=2), dict(omem=2), dict(plane_dtype=2), dict(resolution=0.0), dict(resolution=-0.2),
-               dict(resolution=nan), dict(resolution=inf), dict(map_lower=(C.c_double * 3)(0.0, nan, 0.0))]
-    for kw in invalid:
+    raw = lib.RawCall(gen, entry, cluster.CubeCorridorIn, cluster.CubeCorridorOut, KEYS, xyz, n, SEG, 6, extras=(info,))
+    call, untouched, out = raw.call, raw.untouched, raw.out
+    last_error = lambda: L.direct_cluster_last_error().decode()
+    for kw in [dict(min_d2=-1), dict(min_d2=-2 ** 31)] + lib.INVALID:
         for floor in ((kw["min_d2"],) if "min_d2" in kw else (0, 4)):   # the plain call's refusals in neutral and in clear mode
             assert call(**dict(kw, min_d2=floor)) == abi.DIRECT_ERR_INVALID, kw
             assert untouched(), kw
-    fresh = cluster.ClusterGenerator(ch.DIMS, max_batch=4, cluster_capacity=64, candidate_capacity=64)
-    try:
-        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "no map" in L.direct_cluster_last_error().decode()
+    with lib.handle_without_map() as fresh:
+        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "no map" in last_error()
         fresh.set_map(ch.crafted_map())
-        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "distance field" in L.direct_cluster_last_error().decode()   # no field
+        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "distance field" in last_error()   # no field
         assert untouched()
         fresh.build_distance_field()
         fresh.set_map(ch.crafted_map())
-        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "distance field" in L.direct_cluster_last_error().decode()   # a stale one
+        assert call(h=fresh.h) == abi.DIRECT_ERR_INVALID and "distance field" in last_error()   # a stale one
         assert untouched()
         fresh.build_distance_field(cap_vox=3)
-        assert call(h=fresh.h, min_d2=10) == abi.DIRECT_ERR_INVALID and "cap2" in L.direct_cluster_last_error().decode()
+        assert call(h=fresh.h, min_d2=10) == abi.DIRECT_ERR_INVALID and "cap2" in last_error()
         assert untouched()
         assert call(h=fresh.h, min_d2=9) == abi.DIRECT_OK and info.tolist() == [1, BELOW[9]]
         capped = {k: v.copy() for k, v in out.items()}
-    finally:
-        fresh.close()
     assert call(min_d2=9) == abi.DIRECT_OK and (out["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
     same(out, capped)
     # a NULL info and NULL outputs are left alone: only the codes
-    only = np.full(4, -1, np.int32)
-    par = cluster.CubeCorridorIn(batch=4, path_capacity=CAP, mem_in=abi.MEM_HOST, itr_inflate_max=1000, path_xyz=xyz.ctypes.data,
-                                 path_len=n.ctypes.data, pop_back=1, seg_capacity=SEG, p_max=6, plane_dtype=abi.F64, resolution=RES,
-                                 map_lower=(C.c_double * 3)(*LOWER))
-    o = cluster.CubeCorridorOut(abi.MEM_HOST, 0, None, None, None, None, None, None, only.ctypes.data)
-    assert L.direct_cluster_cube_corridor_clear_batch(gen.h, C.addressof(par), 4, C.addressof(o), None) == abi.DIRECT_OK and not only.any()
+    status, only = raw.only_codes(info=None)
+    assert status == abi.DIRECT_OK and not only.any()
 
 
 def test_cache_of_floor_tables(rows):
@@ -212,15 +178,8 @@ def test_launch_shape_independence_and_bystanders(gen, rows):
     """6.  one call, two halves and a permuted batch give identical bytes; resident clusters, a grid-path result, the field and the
     PLAIN call's result from before are what they are after"""
     xyz, n = ch.pack_paths(rows, CAP)
-    seeds = np.array([[5, 5, 5], [20, 3, 3], [13, 4, 4], [15, 12, 5]], np.int32)
-    starts, goals = np.array([[5, 5, 5], [1, 1, 1]], np.int32), np.array([[22, 18, 10], [20, 12, 5]], np.int32)
     want_plain = gen.cube_corridors(xyz, n, LOWER, RES, seg_capacity=SEG)
-    want_field = gen.distance_field()
-    dev_path = gen.grid_paths(starts, goals, path_capacity=64, mem="device")
-    keep = {k: v.clone() for k, v in dev_path.items()}
-    gen.polygon_generation(seeds, 1000, 0, fetch_clusters=False)
-    want_hull = gen.hull_planes(RES, LOWER, batch=len(seeds), plane_capacity=64, vertex_capacity=64)
-    gen.polygon_generation(seeds, 1000, 0, fetch_clusters=False)
+    by = lib.Bystanders(gen)
 
     one = gen.cube_corridors_clear(xyz, n, LOWER, RES, 4, seg_capacity=SEG)
     h = len(rows) // 2
@@ -229,19 +188,10 @@ def test_launch_shape_independence_and_bystanders(gen, rows):
     same({k: np.concatenate([a[k], b[k]]) for k in KEYS}, one)
     perm = np.random.default_rng(1).permutation(len(rows))
     same(gen.cube_corridors_clear(xyz[perm], n[perm], LOWER, RES, 4, seg_capacity=SEG), {k: one[k][perm] for k in KEYS})
-    gen.cube_corridors_clear(dev_path["path_xyz"], dev_path["path_len"], LOWER, RES, 9, seg_capacity=SEG)
+    gen.cube_corridors_clear(by.dev_path["path_xyz"], by.dev_path["path_len"], LOWER, RES, 9, seg_capacity=SEG)
     same(gen.cube_corridors_clear(xyz, n, LOWER, RES, 4, seg_capacity=SEG), one)
 
-    got_hull = gen.hull_planes(RES, LOWER, batch=len(seeds), plane_capacity=64, vertex_capacity=64)
-    assert (want_hull["rtn"] == cluster.HULL_OK).all()
-    for k in ("rtn", "n_planes", "n_vertices", "degenerate", "center"):
-        assert np.array_equal(want_hull[k], got_hull[k]), k
-    for i in range(len(seeds)):
-        assert np.array_equal(want_hull["planes"][i], got_hull["planes"][i]) and np.array_equal(want_hull["vertices"][i], got_hull["vertices"][i])
-    for k, v in dev_path.items():
-        assert v.cpu().numpy().tobytes() == keep[k].cpu().numpy().tobytes(), k
-    assert np.array_equal(gen.distance_field(), want_field)   # still valid, still the same
-    assert np.array_equal(gen.get_map(), ch.crafted_map())
+    by.check()
     same(gen.cube_corridors(xyz, n, LOWER, RES, seg_capacity=SEG), want_plain)
     assert one["cube_idx"].tobytes() != want_plain["cube_idx"].tobytes()
 
@@ -275,39 +225,16 @@ def test_chain_on_the_device_into_the_optimiser(built):
     B = int(pick.numel())
     assert B >= 2, (cor["rtn"].cpu(), cor["n_seg"].cpu(), paths["rtn"].cpu())
     # the guarantee, on what the device wrote
-    hc = to_host({k: cor[k] for k in KEYS})
+    hc = lib.to_host({k: cor[k] for k in KEYS})
     plen, pd2 = paths["path_len"].cpu().numpy(), paths["path_d2"].cpu().numpy()
     good = np.flatnonzero(hc["rtn"] == cluster.CUBE_CORRIDOR_OK)
     checked, large = cl.guarantee(hc["cube_idx"][good], hc["n_seg"][good], np.rint((hc["seeds"][good] - LOWER) / RES - 0.5).astype(int), d2, FLOOR)
     assert checked >= 2 * B and large >= 1
     for b in np.flatnonzero(paths["rtn"].cpu().numpy() == cluster.GRID_PATH_OK):
         assert (pd2[b, 1:plen[b]] >= FLOOR).all(), b
-    centre = lambda v: v.to(torch.float64) * RES + 0.5 * RES + torch.from_numpy(LOWER).to(dev)
-    last = (paths["path_len"][pick] - 1).long()
-    x0, xd = torch.zeros((B, 9), dtype=torch.float64, device=dev), torch.zeros((B, 9), dtype=torch.float64, device=dev)
-    x0[:, :3] = centre(paths["path_xyz"][pick, 0])
-    xd[:, :3] = centre(paths["path_xyz"][pick, last])
-    t = dict(n_seg=cor["n_seg"][pick].contiguous(), x0=x0, xd=xd, n_planes=cor["n_planes"][pick].contiguous(),
-             planes=cor["planes"][pick].contiguous(), seeds=cor["seeds"][pick].contiguous())
-    cin = abi.BatchIn()
-    cin.batch, cin.n_seg_max, cin.p_max, cin.mem = B, N, P, abi.MEM_DEVICE
-    for k, v in t.items():
-        setattr(cin, k, v.data_ptr())
-    p0, p1 = abi.phase0_params(iter_max=20), abi.phase1_params(iter_max=20)
-    s = solver.DdpSolver(B, N, P, np.float64, device=0)
-    o0, o1 = devmem.DeviceResult(B, N, np.float64, dev), devmem.DeviceResult(B, N, np.float64, dev)
-    torch.cuda.synchronize()
-    s.plan_device(p0, p1, cin, o0.cout, o1.cout)
-    torch.cuda.synchronize()
-    h = {k: v.cpu().numpy() for k, v in t.items()}
-    hb = abi.HostBatch(h["n_seg"], h["x0"], h["xd"], np.zeros((B, N)), h["n_planes"], h["planes"], seeds=h["seeds"]).without_T0()
-    r0, r1 = s.plan(p0, p1, hb)
-    s.close()
-    d0, d1 = o0.to_host(), o1.to_host()
+    x0, xd = lib.chain_ends(paths, pick)
+    h, (_, r1), _ = lib.plan_chain({k: cor[k][pick] for k in ("n_seg", "n_planes", "planes", "seeds")}, x0, xd, N, P)
     print("chain: %d rows, n_seg %s, rtn %s" % (B, h["n_seg"].tolist(), r1.rtn.tolist()))
-    for dv, hv in ((d0, r0), (d1, r1)):
-        for k in ("rtn", "iter_used", "fwd_passes", "cost", "T", "bez", "poly"):
-            assert np.asarray(getattr(dv, k)).tobytes() == np.asarray(getattr(hv, k)).tobytes(), k
     assert (h["n_seg"] <= N).all()
 
 
@@ -315,23 +242,10 @@ def test_cpp_mirror_against_the_python_call(gen, rows, tmp_path):
     """8.  polyhedronGenerator::cubeCorridorClearBatch (direct_amd/host/poly_utils.hpp) fills its corridors with the planes, centres
     and seeds of cube_corridors_clear, bit for bit, for both walks (tests/cpp/test_cube_corridor_clear_gen.cpp)"""
     FLOOR = 4
-    fin, exe = str(tmp_path / "in.bin"), str(tmp_path / "gen")
     xyz, n = ch.pack_paths(rows, CAP)
-    with open(fin, "wb") as f:
-        f.write(struct.pack("<3id3di", *ch.DIMS, RES, *LOWER, len(rows)))
-        for p in rows:
-            f.write(struct.pack("<i", len(p)))
-            f.write(np.ascontiguousarray(p.astype(np.float64) * RES + 0.5 * RES + LOWER, np.float64).tobytes())
-        f.write(ch.crafted_map().tobytes())
-        f.write(struct.pack("<2i", FLOOR, CAP))
-        for pop_back in (True, False):
-            r = gen.cube_corridors_clear(xyz, n, LOWER, RES, FLOOR, pop_back=pop_back, seg_capacity=CAP)
-            assert (r["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
-            for k in ("n_seg", "planes", "centers", "seeds"):
-                f.write(np.ascontiguousarray(r[k]).tobytes())
-    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests/cpp/test_cube_corridor_clear_gen.cpp"), "-o", exe,
-                           "-L" + os.path.join(ROOT, "direct_amd/lib"), "-ldirect_ddp",
-                           "-Wl,-rpath," + os.path.join(ROOT, "direct_amd/lib") + ":/opt/rocm/lib"])
-    out = subprocess.run([exe, fin], capture_output=True, text=True)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    tail = struct.pack("<2i", FLOOR, CAP)
+    for pop_back in (True, False):
+        r = gen.cube_corridors_clear(xyz, n, LOWER, RES, FLOOR, pop_back=pop_back, seg_capacity=CAP)
+        assert (r["rtn"] == cluster.CUBE_CORRIDOR_OK).all()
+        tail += b"".join(np.ascontiguousarray(r[k]).tobytes() for k in ("n_seg", "planes", "centers", "seeds"))
+    lib.run_cpp_mirror(tmp_path, "test_cube_corridor_clear_gen.cpp", rows, tail)

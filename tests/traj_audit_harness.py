@@ -6,6 +6,8 @@ import subprocess
 
 import numpy as np
 
+from tests.cpp_program import compile_program
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 HARNESS = r'''
@@ -94,14 +96,7 @@ ROW_FIELDS = ("vpeak", "apeak", "jpeak", "vnorm", "anorm", "jnorm", "cpeak")
 
 
 def build(workdir):
-    """-ffp-contract=off: the header's multiply-adds are explicit fma() calls and nothing else may be fused, whatever the host's
-    instruction set (the kernels are compiled with contraction switched off per function)"""
-    src = os.path.join(str(workdir), "audit_harness.cpp")
-    exe = os.path.join(str(workdir), "audit_harness")
-    with open(src, "w") as f:
-        f.write(HARNESS)
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Werror", "-I", os.path.join(ROOT, "direct_amd", "csrc"), src, "-o", exe])
-    return str(workdir), exe
+    return str(workdir), compile_program(workdir, "audit_harness", HARNESS)
 
 
 def run(harness, n_seg, T, coef, src, n_planes=None, planes=None, limits=(0.0, 0.0, 0.0, 0.0), on_norm=0, norms=1, cost=None,

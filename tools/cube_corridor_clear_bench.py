@@ -7,7 +7,7 @@ device-resident paths of ONE grid_paths_clear call with the floor:
   (d) the table build alone: a cold call for ONE row of ONE voxel, against the table part of a change of map in the same run
       (direct_cluster_map_from_cloud adding no points: its timed part is then the counters' reset and the table build);
   (e) polytopes per row, plain against clear.
-(b) must equal the g++ build of its arithmetic (tests/cube_corridor_clear_harness.py) and, for the witness, the plain call of a
+(b) must equal the g++ build of its arithmetic (tests/cube_corridor_harness.py, floor-filled) and, for the witness, the plain call of a
 second handle holding the thresholded field as its map.
 usage: cube_corridor_clear_bench.py [out.json]   (default profiles/cube_corridor_clear_bench.json)"""
 import json
