@@ -24,7 +24,16 @@ class MapCloud(C.Structure):  # direct_map_cloud_t
 class MapScan(C.Structure):  # direct_map_scan_t
     _fields_ = [("map_lower", C.c_double * 3), ("map_upper", C.c_double * 3), ("resolution", C.c_double), ("max_range", C.c_double),
                 ("origin", C.c_double * 3), ("inflate", C.c_int32 * 3), ("mode", C.c_int32), ("stride", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("flags", C.c_int32)]
+
+
+class FrontierIn(C.Structure):  # direct_frontier_in_t
+    _fields_ = [("min_d2", C.c_int32), ("min_size", C.c_int32), ("capacity", C.c_int32), ("mem", C.c_int32)]
+
+
+class FrontierOut(C.Structure):  # direct_frontier_out_t
+    _fields_ = [("label", C.c_void_p), ("size", C.c_void_p), ("centroid", C.c_void_p), ("rep", C.c_void_p), ("voxel_label", C.c_void_p),
+                ("stats", C.c_void_p)]
 
 
 class PlanCheckIn(C.Structure):  # direct_plan_check_in_t
@@ -54,13 +63,16 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_cube_corridor_batch", "direct_cluster_grid_path_clear_batch", "direct_cluster_grid_path_fan_batch",
            "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
            "direct_cluster_reachable_batch", "direct_cluster_corridor_batch", "direct_cluster_map_integrate_scan",
-           "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms")
+           "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms", "direct_cluster_get_known", "direct_cluster_set_known",
+           "direct_cluster_frontier", "direct_cluster_frontier_phase_ms")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
 MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
 SCAN_RESET, SCAN_CONTINUE, SCAN_ADOPT = 0, 1, 2
+SCAN_TRACK_KNOWN = 1   # direct_map_scan_t.flags
+FRONTIER_STATS = ("known", "frontier", "components", "kept", "written", "largest")   # stats[6]
 SCAN_STATS = ("points", "skipped_nonfinite", "truncated", "outside", "raw_occupied", "occupied", "set", "cleared")   # stats[8]
 PLAN_CHECK_INVALID = -1
 DIST_NONE = 0x7fffffff
@@ -105,6 +117,10 @@ def _lib():
         L.direct_cluster_map_integrate_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.direct_cluster_get_scan_grid.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_scan_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.direct_cluster_get_known.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_set_known.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_frontier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_frontier_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -183,19 +199,22 @@ class ClusterGenerator:
         assert pts.ndim == 2 and pts.shape[1] in (3, 4), "points must have shape [n, 3] or [n, 4]"
         return pts, mem, ptr
 
-    def integrate_scan(self, points, origin, map_lower, resolution, max_range, inflate=(0, 0, 0), mode="continue", map_upper=None):
+    def integrate_scan(self, points, origin, map_lower, resolution, max_range, inflate=(0, 0, 0), mode="continue", map_upper=None,
+                       track_known=False):
         """One sensor scan folded into the resident map (direct_cluster_map_integrate_scan): every ray from origin to a point
         carves the scan grid free, every return within max_range marks its voxel, and the map is the scan grid dilated by the
         voxel box inflate.  points as in set_map_from_cloud.  mode: "reset" (the scan grid starts empty), "continue" (keep it) or
         "adopt" (it starts as the map the handle holds).  The field, the floor tables and the components stay valid when
-        set + cleared == 0; rebuild them otherwise.
+        set + cleared == 0; rebuild them otherwise.  track_known: every voxel the scan carves or marks is also recorded in the
+        resident known grid (known_grid, frontiers); an untracked scan drops a known grid the handle holds.
         -> dict(points, skipped_nonfinite, truncated, outside, raw_occupied, occupied, set, cleared)"""
         lower = np.asarray(map_lower, np.float64).reshape(3)
         upper = lower + np.asarray(self.dims, np.float64) * float(resolution) if map_upper is None else np.asarray(map_upper, np.float64).reshape(3)
         pts, mem, ptr = self._cloud(points)
         par = MapScan((C.c_double * 3)(*lower), (C.c_double * 3)(*upper), float(resolution), float(max_range),
                       (C.c_double * 3)(*np.asarray(origin, np.float64).reshape(3)), (C.c_int32 * 3)(*[int(v) for v in inflate]),
-                      {"reset": SCAN_RESET, "continue": SCAN_CONTINUE, "adopt": SCAN_ADOPT}[mode], int(pts.shape[1]), 0)
+                      {"reset": SCAN_RESET, "continue": SCAN_CONTINUE, "adopt": SCAN_ADOPT}[mode], int(pts.shape[1]),
+                      SCAN_TRACK_KNOWN if track_known else 0)
         n = int(pts.shape[0])
         stats = np.zeros(8, np.int64)
         _check(_lib().direct_cluster_map_integrate_scan(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
@@ -207,6 +226,68 @@ class ClusterGenerator:
         g = np.zeros(self.dims, np.uint8)
         _check(_lib().direct_cluster_get_scan_grid(self.h, abi.MEM_HOST, g.ctypes.data))
         return g
+
+    def known_grid(self):
+        """The known grid as a uint8 array of shape dims (direct_cluster_get_known): 1 where a tracked scan has carved or marked
+        (or set_known said so), 0 where nothing has been observed"""
+        g = np.zeros(self.dims, np.uint8)
+        _check(_lib().direct_cluster_get_known(self.h, abi.MEM_HOST, g.ctypes.data))
+        return g
+
+    def set_known(self, known):
+        """The known grid becomes (known != 0) of a NumPy array or device tensor of shape dims, uint8; None: all zero
+        (direct_cluster_set_known) - a persisted grid, a declared-known box around the take-off point, a prior map"""
+        if known is None:
+            mem, ptr = abi.MEM_HOST, None
+        elif isinstance(known, np.ndarray) or not hasattr(known, "data_ptr"):
+            known = np.ascontiguousarray(known, np.uint8)
+            mem, ptr = abi.MEM_HOST, known.ctypes.data
+        else:
+            import torch
+            known = known.to(torch.uint8).contiguous()
+            assert known.is_cuda
+            torch.cuda.current_stream(known.device).synchronize()  # the handle's stream is not torch's
+            mem, ptr = abi.MEM_DEVICE, known.data_ptr()
+        assert known is None or tuple(known.shape) == self.dims
+        _check(_lib().direct_cluster_set_known(self.h, mem, ptr))
+
+    def frontiers(self, min_size=1, min_d2=0, capacity=1024, mem="host", voxel_labels=False):
+        """Goal voxels on the boundary between observed and unobserved space (direct_cluster_frontier): the 26-connected components
+        of the known, enterable voxels (map byte 0 and, for min_d2 > 1, stored D2 >= min_d2) with an unknown face neighbour inside
+        the map; those of at least min_size voxels, in ascending label order, the first `capacity` of them.
+        -> dict(label [k], size [k], centroid [k][3], rep [k][3], stats: dict(known, frontier, components, kept, written, largest)
+        and, with voxel_labels, voxel_label of shape dims), k = written.  rep is a member of its component: known, enterable and a
+        legal goal of reachable / grid_paths_fan under the same floor.  mem="device": tensors (stats stays a dict)."""
+        assert mem in ("host", "device")
+        cap = int(capacity)
+        if mem == "device":
+            import torch
+            z = lambda shape: torch.zeros(shape, dtype=torch.int32, device="cuda:%d" % self.device)
+            ptr = lambda a: a.data_ptr()
+        else:
+            z = lambda shape: np.zeros(shape, np.int32)
+            ptr = lambda a: a.ctypes.data
+        out = dict(label=z(max(cap, 0)), size=z(max(cap, 0)), centroid=z((max(cap, 0), 3)), rep=z((max(cap, 0), 3)))
+        vox = z(self.dims) if voxel_labels else None
+        if mem == "device":
+            torch.cuda.current_stream(out["label"].device).synchronize()  # the handle's stream is not torch's
+        stats = np.zeros(6, np.int64)
+        par = FrontierIn(int(min_d2), int(min_size), cap, abi.MEM_DEVICE if mem == "device" else abi.MEM_HOST)
+        o = FrontierOut(*[ptr(out[k]) if cap > 0 else None for k in ("label", "size", "centroid", "rep")], None if vox is None else ptr(vox),
+                        stats.ctypes.data)
+        _check(_lib().direct_cluster_frontier(self.h, C.addressof(par), C.addressof(o)))
+        k = int(stats[4])
+        out = {key: a[:k] for key, a in out.items()}
+        out["stats"] = dict(zip(FRONTIER_STATS, (int(v) for v in stats)))
+        if voxel_labels:
+            out["voxel_label"] = vox
+        return out
+
+    def frontier_phase_ms(self):
+        """[mask, labelling, compaction, goals] ms of the last frontiers call; needs DIRECT_CLUSTER_SCAN_TIMING=1 at creation"""
+        ms = (C.c_float * 4)()
+        _check(_lib().direct_cluster_frontier_phase_ms(self.h, ms))
+        return [float(v) for v in ms]
 
     def scan_phase_ms(self):
         """[carve, mark, inflate, table] ms of the last scan; the handle must have been created with DIRECT_CLUSTER_SCAN_TIMING=1"""

@@ -33,6 +33,7 @@
 #include "cube_corridor_clear_math.h"
 #include "cube_corridor_math.h"
 #include "free_comp_math.h"
+#include "frontier_math.h"
 #include "grid_path_clear_math.h"
 #include "grid_path_fan_math.h"
 #include "grid_path_math.h"
@@ -998,6 +999,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "free_comp.h"
 #include "cluster_corridor.h"
 #include "map_scan.h"
+#include "frontier.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1058,6 +1060,13 @@ struct direct_cluster_handle_s {
   bool scan_timing = false;               // record the phases' events (DIRECT_CLUSTER_SCAN_TIMING=1: tools/map_scan_bench.py)
   hipEvent_t scan_ev[5] = {};             // before the carve, behind the carve, the mark, the inflation and the table
   float scan_ms[4] = {0, 0, 0, 0};        // what they measured in the last call (the table: 0 when it was not rebuilt)
+  uint8_t* known = nullptr;               // the known grid (the map's size and layout), allocated by the first tracked scan or set_known
+  hs::Block known_in;                     // device staging of set_known's host bytes
+  hs::Block front_ws;                     // workspace of frontier (mask, labels, sizes, slot grid, workgroup counts, counters), grown on demand
+  hs::Block front_out;                    // its slot arrays and the device staging of its host outputs, grown with capacity
+  hipEvent_t front_ev[5] = {};            // scan_timing: before the mask, behind the mask, the labelling, the compaction and the goals
+  float front_ms[4] = {0, 0, 0, 0};
+  bool front_timed = false;
 };
 
 namespace {
@@ -1540,9 +1549,12 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   (void)hipDeviceSynchronize();
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
-                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out, &h->scan_ws})
+                       &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out, &h->scan_ws,
+                       &h->known_in, &h->front_ws, &h->front_out})
     hs::release(*b);
   for (hipEvent_t e : h->scan_ev)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->front_ev)
     if (e) (void)hipEventDestroy(e);
   hs::destroy(h->ev);
   delete h;
@@ -1628,6 +1640,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
   const char* why = cloud_refusal(n_points, mem, xyz);
   if (!why && p->mode != DIRECT_SCAN_RESET && p->mode != DIRECT_SCAN_CONTINUE && p->mode != DIRECT_SCAN_ADOPT) why = "unknown mode";
+  if (!why && !ms::flags_known(p->flags)) why = "unknown flags";
   if (!why) why = stride_refusal(p->stride);
   if (!why) why = resolution_refusal(p->resolution);
   if (why) return cfail(DIRECT_ERR_INVALID, why);
@@ -1654,9 +1667,11 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   const size_t cells = (size_t)D.G;
   if (!h->scan_raw)
     CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->scan_raw, cells), hs::want(&h->scan_cnt, kScanCounters * sizeof(unsigned long long))}));
+  const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
+  if (track && !h->known) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->known, cells)}));
   if (h->scan_timing && !h->scan_ev[0])
     for (hipEvent_t& e : h->scan_ev) CHIP_TRY(hipEventCreate(&e));
-  S.n = n_points; S.stride = p->stride; S.raw = h->scan_raw; S.cnt = h->scan_cnt;
+  S.n = n_points; S.stride = p->stride; S.raw = h->scan_raw; S.cnt = h->scan_cnt; S.known = track ? h->known : nullptr;
   if (p->inflate[1] > 0 || p->inflate[2] > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, 2 * cells));
   if (const direct_status_t rc = cloud_on_device(h, n_points, p->stride, mem, xyz, &S.xyz)) return rc;
   const bool had_map = h->rs.has_map();
@@ -1668,17 +1683,21 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     if (p->mode == DIRECT_SCAN_ADOPT) e = hipMemcpyAsync(h->scan_raw, h->map, cells, hipMemcpyDeviceToDevice, h->stream);
     else if (p->mode == DIRECT_SCAN_RESET || !h->rs.has_scan_grid()) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
   }
+  if (e == hipSuccess && track && (p->mode == DIRECT_SCAN_RESET || !h->rs.has_known())) e = hipMemsetAsync(h->known, 0, cells, h->stream);
   h->rs.scan_began();  // no scan grid until the call has ended well
+  if (track) h->rs.known_scan_began();  // ... and no known grid
+  else h->rs.known_dropped();           // the rays of an untracked scan are not recorded: a known grid no longer describes what was seen
   const int ray_blocks = (int)std::min<long long>((n_points + 255) / 256, kScanMaxBlocks);
   if (e == hipSuccess) e = tick(0);
   if (e == hipSuccess && n_points > 0) {
-    if (h->scan_test_store) hipLaunchKernelGGL(k_scan_carve<true>, dim3(ray_blocks), dim3(256), 0, h->stream, S);
-    else hipLaunchKernelGGL(k_scan_carve<false>, dim3(ray_blocks), dim3(256), 0, h->stream, S);
+    auto carve = h->scan_test_store ? (track ? k_scan_carve<true, true> : k_scan_carve<true, false>)
+                                    : (track ? k_scan_carve<false, true> : k_scan_carve<false, false>);
+    hipLaunchKernelGGL(carve, dim3(ray_blocks), dim3(256), 0, h->stream, S);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = tick(1);
   if (e == hipSuccess && n_points > 0) {
-    hipLaunchKernelGGL(k_scan_mark, dim3(ray_blocks), dim3(256), 0, h->stream, S);
+    hipLaunchKernelGGL(track ? k_scan_mark<true> : k_scan_mark<false>, dim3(ray_blocks), dim3(256), 0, h->stream, S);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = tick(2);
@@ -1710,9 +1729,11 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&h->scan_ms[k], h->scan_ev[k], h->scan_ev[k + 1]);
   if (e != hipSuccess) {  // the map and the scan grid have been touched: nothing describes them any more
     h->rs.scan_ended(rs::ScanEnd::failed);
+    if (track) h->rs.known_ended(false);
     return cfail(DIRECT_ERR_DEVICE, std::string("map_integrate_scan: ") + hipGetErrorString(e));
   }
   h->rs.scan_ended(changed ? rs::ScanEnd::changed : rs::ScanEnd::unchanged);
+  if (track) h->rs.known_ended(true);
   if (stats) {
     stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
     stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
@@ -2320,6 +2341,141 @@ direct_status_t direct_cluster_reachable_batch(direct_cluster_handle_t h, const 
   if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
   e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
   if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("reachable_batch: ") + hipGetErrorString(e));
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_known(direct_cluster_handle_t h, int32_t mem, uint8_t* known) {
+  if (!h || !known) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_known()) return cfail(DIRECT_ERR_INVALID, "the handle has no known grid");
+  return fetch_resident(h, mem, (size_t)h->D.G, known, h->known);
+}
+
+direct_status_t direct_cluster_set_known(direct_cluster_handle_t h, int32_t mem, const uint8_t* known) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->D.G;
+  if (!h->known) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->known, cells)}));
+  const uint8_t* src = known;
+  if (known && mem == DIRECT_MEM_HOST) {
+    CHIP_TRY(hs::grow(h->known_in, h->stream, cells));
+    src = (const uint8_t*)h->known_in.p;
+  }
+  h->rs.known_dropped();  // the grid is about to be written: not present until the call has drained
+  hipError_t e = hipSuccess;
+  if (!known) {
+    e = hipMemsetAsync(h->known, 0, cells, h->stream);
+  } else {
+    if (mem == DIRECT_MEM_HOST) e = hipMemcpyAsync(h->known_in.p, known, cells, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+      const int blocks = (int)std::min<long long>(((long long)cells + 255) / 256, kScanMaxBlocks);
+      hipLaunchKernelGGL(k_known_set, dim3(blocks), dim3(256), 0, h->stream, h->known, src, (long long)cells);
+      e = hipGetLastError();
+    }
+  }
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("set_known: ") + hipGetErrorString(e));
+  h->rs.known_set();
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_frontier(direct_cluster_handle_t h, const direct_frontier_in_t* in, const direct_frontier_out_t* out) {
+  if (!h || !in || !out) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(in->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (in->min_d2 < 0) return cfail(DIRECT_ERR_INVALID, "min_d2 must not be negative");
+  if (in->min_size < 1) return cfail(DIRECT_ERR_INVALID, "min_size must be at least 1");
+  if (in->capacity < 0) return cfail(DIRECT_ERR_INVALID, "capacity must not be negative");
+  if (in->capacity > 0 && !out->label && !out->size && !out->centroid && !out->rep)
+    return cfail(DIRECT_ERR_INVALID, "capacity without a per-component output: pass one of label, size, centroid, rep, or capacity 0");
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_known()) return cfail(DIRECT_ERR_INVALID, "the handle has no known grid");
+  const int32_t floor = fc::normal_floor(in->min_d2);
+  if (floor)
+    if (const char* why = h->rs.field_refusal(floor, 0)) return cfail(DIRECT_ERR_INVALID, why);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const Dev& D = h->D;
+  const size_t G = (size_t)D.G, nb = (G + 255) / 256;
+  FrontDev F = {};
+  F.map = h->map; F.known = h->known; F.d2 = floor ? h->dist[0] : nullptr;
+  F.X = D.max_x; F.Y = D.max_y; F.Z = D.max_z; F.G = D.G; F.nb = (int)nb;
+  F.min_d2 = floor; F.min_size = in->min_size;
+  F.capacity = (int)std::min<size_t>((size_t)in->capacity, G);  // no more components than voxels: the slot arrays need no more
+  // the workspace of G-sized grids: words first, the mask's bytes last
+  unsigned long long* lab_cnt = nullptr;
+  {
+    const size_t words = (4 + kFrontCounters) * sizeof(unsigned long long) + (3 * G + nb) * sizeof(int32_t);
+    CHIP_TRY(hs::grow(h->front_ws, h->stream, words + G));
+    char* q = (char*)h->front_ws.p;
+    lab_cnt = (unsigned long long*)q; F.cnt = lab_cnt + 4; q += (4 + kFrontCounters) * sizeof(unsigned long long);
+    F.label = (int32_t*)q; q += G * sizeof(int32_t);
+    F.size = (int32_t*)q; q += G * sizeof(int32_t);
+    F.slot = (int32_t*)q; q += G * sizeof(int32_t);
+    F.wg = (int32_t*)q; q += nb * sizeof(int32_t);
+    F.mask = (uint8_t*)q;
+  }
+  const size_t cap = (size_t)F.capacity;
+  hs::Stage so(in->mem == DIRECT_MEM_HOST);
+  hs::stage_scratch(so, &F.s_sum, cap * 3 * sizeof(unsigned long long));
+  hs::stage_scratch(so, &F.s_key, cap * sizeof(unsigned long long));
+  hs::stage_scratch(so, &F.s_label, cap * sizeof(int32_t));
+  hs::stage_scratch(so, &F.s_size, cap * sizeof(int32_t));
+  hs::stage_out(so, &F.o_label, out->label, cap * sizeof(int32_t), 0xff);
+  hs::stage_out(so, &F.o_size, out->size, cap * sizeof(int32_t), 0xff);
+  hs::stage_out(so, &F.o_centroid, out->centroid, cap * 3 * sizeof(int32_t), 0xff);
+  hs::stage_out(so, &F.o_rep, out->rep, cap * 3 * sizeof(int32_t), 0xff);
+  CHIP_TRY(hs::stage_upload(so, h->front_out, h->stream));
+  if (h->scan_timing && !h->front_ev[0])
+    for (hipEvent_t& ev : h->front_ev) CHIP_TRY(hipEventCreate(&ev));
+  h->front_timed = false;
+  auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->front_ev[k], h->stream) : hipSuccess; };
+  CompDev A = {};
+  A.map = F.mask; A.d2 = nullptr; A.label = F.label; A.size = F.size; A.cnt = lab_cnt;
+  A.X = F.X; A.Y = F.Y; A.Z = F.Z; A.G = F.G; A.min_d2 = 0;
+  A.tx = gp::tiles_along(A.X); A.ty = gp::tiles_along(A.Y); A.tz = gp::tiles_along(A.Z);
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(lab_cnt, 0, (4 + kFrontCounters) * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(F.size, 0, G * sizeof(int32_t), h->stream);
+  if (e == hipSuccess && cap) e = hipMemsetAsync(F.s_sum, 0, cap * 3 * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess && cap) e = hipMemsetAsync(F.s_key, 0xff, cap * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = tick(0);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_front_mask, dim3(F.nb), dim3(256), 0, h->stream, F);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(1);
+  if (e == hipSuccess) e = free_comp_launch(A, h->stream);
+  if (e == hipSuccess) e = tick(2);
+  if (e == hipSuccess) e = front_compact_launch(F, h->stream);
+  if (e == hipSuccess) e = tick(3);
+  if (e == hipSuccess) e = front_goals_launch(F, h->stream);
+  if (e == hipSuccess) e = tick(4);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  unsigned long long cnt[4 + kFrontCounters] = {};
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt, lab_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && out->voxel_label)
+    e = hipMemcpyAsync(out->voxel_label, F.label, G * sizeof(int32_t), in->mem == DIRECT_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice,
+                       h->stream);
+  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
+  if (e == hipSuccess && h->scan_timing) {
+    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&h->front_ms[k], h->front_ev[k], h->front_ev[k + 1]);
+    h->front_timed = e == hipSuccess;
+  }
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("frontier: ") + hipGetErrorString(e));
+  if (cnt[3]) return cfail(DIRECT_ERR_DEVICE, "frontier: a union-find loop passed its trip bound (error word " + std::to_string(cnt[3]) + ")");
+  if (out->stats) {
+    const unsigned long long kept = cnt[4 + kFrontKept];
+    out->stats[0] = (int64_t)cnt[4 + kFrontKnown]; out->stats[1] = (int64_t)cnt[4 + kFrontVoxels]; out->stats[2] = (int64_t)cnt[1];
+    out->stats[3] = (int64_t)kept; out->stats[4] = (int64_t)std::min<unsigned long long>(kept, (unsigned long long)in->capacity);
+    out->stats[5] = fc::stat_size(cnt[2]);
+  }
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_frontier_phase_ms(direct_cluster_handle_t h, float* ms4) {
+  if (!h || !ms4) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!h->scan_timing || !h->front_timed) return cfail(DIRECT_ERR_INVALID, "no timed frontier call: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
+  for (int k = 0; k < 4; k++) ms4[k] = h->front_ms[k];
   return DIRECT_OK;
 }
 

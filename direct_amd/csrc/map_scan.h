@@ -11,6 +11,10 @@
 // Neighbouring points of a real scan walk neighbouring voxels and every ray crosses the voxels around the origin; the launch
 // file's map (3.7 MB) fits one XCD's 4 MB L2, which absorbs the scatter.  kTest chooses between storing 0 unconditionally and
 // loading the byte first and storing only where it is not 0 yet (tools/map_scan_bench.py times both).
+// kKnown (DIRECT_SCAN_TRACK_KNOWN) adds the known grid: the carve's lambda and the mark store the byte 1 into it at the very index
+// they write the scan grid at, under the same kTest choice.  Every writer of the known grid writes 1, in both phases: the known
+// grid depends neither on the order of the points nor on the launch shape.  kKnown = false is the code without the known grid.
+// k_known_set copies a caller's known grid in, one lane per voxel, as src != 0.
 // Counters: one shuffle reduction per wave, then one 64-bit integer atomic per wave and counter, as in k_cloud_raster.
 #pragma once
 #include "map_scan_math.h"
@@ -27,6 +31,7 @@ struct ScanDev {
   const float* xyz;        // [n][stride]
   uint8_t* raw;            // the scan grid, [size[0] * size[1] * size[2]]
   unsigned long long* cnt; // [kScanCounters]
+  uint8_t* known;          // the known grid in the scan grid's layout; read and written by the kKnown instantiations only
 };
 
 __device__ __forceinline__ void scan_count(unsigned long long v, unsigned long long* where) {
@@ -34,14 +39,16 @@ __device__ __forceinline__ void scan_count(unsigned long long v, unsigned long l
   if ((threadIdx.x & 63) == 0 && v) atomicAdd(where, v);
 }
 
-template <bool kTest>
+template <bool kTest, bool kKnown>
 __global__ __launch_bounds__(256) void k_scan_carve(ScanDev S) {
   unsigned long long skipped = 0, truncated = 0;
   uint8_t* raw = S.raw;
+  uint8_t* known = S.known;
   for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < S.n; p += (long long)gridDim.x * blockDim.x) {
     const float* q = S.xyz + p * S.stride;
-    const int kind = ms::carve_ray(S.G, q[0], q[1], q[2], [raw](size_t at) {
+    const int kind = ms::carve_ray(S.G, q[0], q[1], q[2], [raw, known](size_t at) {
       if (!kTest || raw[at] != 0) raw[at] = 0;
+      if (kKnown && (!kTest || known[at] != 1)) known[at] = 1;
     });
     skipped += kind == ms::kSkipped;
     truncated += kind == ms::kTruncated;
@@ -50,6 +57,7 @@ __global__ __launch_bounds__(256) void k_scan_carve(ScanDev S) {
   scan_count(truncated, &S.cnt[kScanTruncated]);
 }
 
+template <bool kKnown>
 __global__ __launch_bounds__(256) void k_scan_mark(ScanDev S) {
   unsigned long long outside = 0;
   for (long long p = blockIdx.x * (long long)blockDim.x + threadIdx.x; p < S.n; p += (long long)gridDim.x * blockDim.x) {
@@ -57,9 +65,14 @@ __global__ __launch_bounds__(256) void k_scan_mark(ScanDev S) {
     size_t at = 0;
     const int m = ms::mark_voxel(S.G, q[0], q[1], q[2], &at);
     if (m > 0) S.raw[at] = 1;
+    if (kKnown && m > 0) S.known[at] = 1;
     outside += m < 0;
   }
   scan_count(outside, &S.cnt[kScanOutside]);
+}
+
+__global__ __launch_bounds__(256) void k_known_set(uint8_t* known, const uint8_t* src, long long G) {
+  for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < G; t += (long long)gridDim.x * blockDim.x) known[t] = src[t] != 0;
 }
 
 struct DilateDev {

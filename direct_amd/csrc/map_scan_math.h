@@ -28,6 +28,11 @@
 // ulp.  This header switches contraction off itself, per function, as map_cloud_math.h does; under g++ the harness passes
 // -ffp-contract=off.
 //
+// THE KNOWN GRID (flags & kTrackKnown) is a second byte per voxel, 1 = observed: every voxel carve_ray hands to `clear` and every
+// voxel mark_voxel returns gets known = 1, at the same voxel() index (the callers write both bytes from the one lambda, there is
+// no second walk).  Every writer of the known grid writes 1, in both phases: it depends neither on the order of the points nor
+// on the launch shape, and needs no ordering between the phases.
+//
 // THE DILATION is a voxel box without wrap, separable: along one axis, dst is 1 exactly when some src voxel within r steps
 // inside the map is 1.  Integers only.
 #pragma once
@@ -43,6 +48,8 @@ namespace mapscan {
 constexpr int kMaxRangeVox = 4096;  // the library refuses max_range * inv above this
 constexpr int kMaxInflate = 64;     // ... and an inflate above this
 constexpr int kSkipped = 0, kHit = 1, kTruncated = 2;  // what classify() returns
+constexpr int kTrackKnown = 1;      // direct_map_scan_t.flags, DIRECT_SCAN_TRACK_KNOWN; every other bit is refused
+DIRECT_MAPCLOUD_HD bool flags_known(int flags) { return (flags & ~kTrackKnown) == 0; }
 
 struct Grid {
   double lower[3], origin[3];

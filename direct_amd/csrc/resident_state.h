@@ -6,8 +6,8 @@
 //
 // Two properties the C boundary depends on:
 //   - All-zero bytes mean "nothing resident": every question answers from a zeroed object (no map, no valid field, no valid
-//     labels, no scan grid, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer as a handle and
-//     assert that a refused call wrote not one byte of it.
+//     labels, no scan grid, no known grid, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer
+//     as a handle and assert that a refused call wrote not one byte of it.
 //   - No pointers, trivially copyable, a few dozen bytes.
 //
 // The field has TWO counters, and they are not one:
@@ -51,6 +51,13 @@ struct State {
     have_map_ = have_scan_ = how != ScanEnd::failed;
   }
   bool has_scan_grid() const { return have_scan_ != 0; }
+
+  // ---- the known grid (what the tracked scans have observed; it describes observation, not occupancy: no map event touches it)
+  void known_scan_began() { have_known_ = 0; }      // a tracked scan writes it: not present until the call has ended well
+  void known_ended(bool ok) { have_known_ = ok; }   // ... which a device error does not
+  void known_set() { have_known_ = 1; }             // set_known has drained: the caller's bytes, or all zero
+  void known_dropped() { have_known_ = 0; }         // an untracked scan past its refusals (its rays were not recorded), a failed set_known
+  bool has_known() const { return have_known_ != 0; }
 
   // ---- the distance field ------------------------------------------------------------------------------------------------
   void field_call_began() { field_gen_++; }    // every distance_field past its null check: labels built with a floor are stale
@@ -104,6 +111,7 @@ struct State {
   cubecor::FloorSlot floor_slot_[cubecor::kFloorSlots];
   freecomp::Key label_key_;              // what the labels were built from (valid == 0: none)
   int32_t clusters_;
+  int32_t have_known_;
 };
 static_assert(std::is_trivially_copyable<State>::value && std::is_standard_layout<State>::value, "plain data: zero bytes are a State");
 static_assert(sizeof(State) <= 256, "a handle is far smaller than the 64 KiB the ABI tests hand over");

@@ -24,6 +24,8 @@
 //     no plane read back between rounds
 //   * buildFreeComponents(min_d2) / reachable(starts, goals) which goals can be reached at all, before any path call runs
 //     (direct_cluster_free_components, direct_cluster_reachable_batch)
+//   * integrateScan(..., track_known) / frontiers(min_size, min_d2, capacity) where the goals of a vehicle that maps as it flies
+//     come from: the boundary between what its scans have observed and what they have not (direct_cluster_frontier)
 // Corridor / Polytope types are template parameters read through the member names of
 // global_planner/include/global_planner/utils/data_type.h:124-245 (polyhedrons, planes, center, seed_coord,
 // appendPlane, setSeed / setCenter where they exist); direct::PlainCorridor of ddp_optimizer.hpp fits.
@@ -86,12 +88,14 @@ class polyhedronGenerator {
   // box inflate (zeros for the radius-aware calls; the radius in voxels for the corridors, which have no floor).  mode:
   // DIRECT_SCAN_RESET, DIRECT_SCAN_CONTINUE, or DIRECT_SCAN_ADOPT after setMap / setCloud.  Unlike setCloud(add = true) a voxel
   // that a later ray passes leaves the map again.  changed() == false: the distance field and the free components still serve.
+  // track_known: the scan also records every voxel it carves or marks in the resident known grid, which frontiers() reads; an
+  // untracked scan drops a known grid the generator holds.
   struct ScanResult {
     long long points = 0, skipped_nonfinite = 0, truncated = 0, outside = 0, raw_occupied = 0, occupied = 0, set = 0, cleared = 0;
     bool changed() const { return set + cleared > 0; }
   };
   ScanResult integrateScan(const float* xyz, int64_t n, int stride, const std::array<double, 3>& origin, double max_range,
-                           const std::array<int, 3>& inflate = {{0, 0, 0}}, int mode = DIRECT_SCAN_CONTINUE) {
+                           const std::array<int, 3>& inflate = {{0, 0, 0}}, int mode = DIRECT_SCAN_CONTINUE, bool track_known = false) {
     direct_map_scan_t p{};
     for (int a = 0; a < 3; a++) {
       p.map_lower[a] = lower_[a];
@@ -103,6 +107,7 @@ class polyhedronGenerator {
     p.max_range = max_range;
     p.mode = mode;
     p.stride = stride;
+    p.flags = track_known ? DIRECT_SCAN_TRACK_KNOWN : 0;
     int64_t s[8];
     if (direct_cluster_map_integrate_scan(h_, &p, n, DIRECT_MEM_HOST, xyz, s) != DIRECT_OK)
       throw std::runtime_error(direct_cluster_last_error());
@@ -111,6 +116,37 @@ class polyhedronGenerator {
     r.points = s[0]; r.skipped_nonfinite = s[1]; r.truncated = s[2]; r.outside = s[3];
     r.raw_occupied = s[4]; r.occupied = s[5]; r.set = s[6]; r.cleared = s[7];
     return r;
+  }
+  // Goal voxels on the boundary between observed and unobserved space (direct_cluster_frontier): the 26-connected components of
+  // the known, enterable voxels with an unknown face neighbour inside the map; those of at least min_size voxels in ascending
+  // label order, the first `capacity` of them.  rep[k] is a member of component k - known, enterable under the floor min_d2 - and
+  // goes straight into reachable() and the path calls as a voxel index.  kept > capacity: call again with more room.
+  struct Frontiers {
+    std::vector<int32_t> label, size;                      // [written]
+    std::vector<std::array<int32_t, 3>> centroid, rep;     // [written]
+    long long known = 0, frontier = 0, components = 0, kept = 0, written = 0, largest = 0;
+  };
+  Frontiers frontiers(int min_size = 1, int min_d2 = 0, int capacity = 1024) {
+    Frontiers f;
+    const size_t cap = capacity > 0 ? (size_t)capacity : 0;
+    f.label.resize(cap); f.size.resize(cap); f.centroid.resize(cap); f.rep.resize(cap);
+    const direct_frontier_in_t in{min_d2, min_size, capacity, DIRECT_MEM_HOST};
+    int64_t s[6];
+    const direct_frontier_out_t out{cap ? f.label.data() : nullptr, cap ? f.size.data() : nullptr, cap ? &f.centroid[0][0] : nullptr,
+                                    cap ? &f.rep[0][0] : nullptr, nullptr, s};
+    if (direct_cluster_frontier(h_, &in, &out) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    f.known = s[0]; f.frontier = s[1]; f.components = s[2]; f.kept = s[3]; f.written = s[4]; f.largest = s[5];
+    f.label.resize((size_t)s[4]); f.size.resize((size_t)s[4]); f.centroid.resize((size_t)s[4]); f.rep.resize((size_t)s[4]);
+    return f;
+  }
+  // the known grid as the generator holds it, [x][y][z] (direct_cluster_get_known); setKnown(nullptr) empties it
+  std::vector<uint8_t> getKnown() {
+    std::vector<uint8_t> m((size_t)mx_ * my_ * mz_);
+    if (direct_cluster_get_known(h_, DIRECT_MEM_HOST, m.data()) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return m;
+  }
+  void setKnown(const uint8_t* known) {
+    if (direct_cluster_set_known(h_, DIRECT_MEM_HOST, known) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
   }
   // the map as the generator holds it, [x][y][z] (direct_cluster_get_map)
   std::vector<uint8_t> getMap() {

@@ -820,7 +820,8 @@ direct_status_t direct_cluster_corridor_batch(direct_cluster_handle_t h, const d
 direct_status_t direct_cluster_set_stream(direct_cluster_handle_t h, void* hip_stream);
 /* HIP-event time [ms] of the kernels of the last polygon_generation_batch / convex_test / hull_planes_batch /
  * grid_path_batch / map_from_cloud / plan_check_batch / distance_field / plan_clearance_batch / cube_corridor_batch /
- * grid_path_clear_batch / grid_path_fan_batch / free_components / reachable_batch / corridor_batch call (the fan: its init,
+ * grid_path_clear_batch / grid_path_fan_batch / free_components / reachable_batch / corridor_batch / map_integrate_scan /
+ * frontier call (the fan: its init,
  * bounds, rounds, read-back and stats kernels with the read-backs of the round counters between them, not the copies of host
  * arrays; the components: the two clears and the four kernels of a build, the one kernel of reachable_batch; corridor_batch:
  * from its first kernel to its last, the waits of its read-backs included) */
@@ -848,8 +849,9 @@ direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
  *               code; the distance field, the floor tables and the free components are stale; resident clusters stay).  If
  *               NOTHING changed, all of them stay valid and nothing is rebuilt: a node that scans a static room at 10 Hz pays
  *               for no field.  Rebuild the field when stats[6] + stats[7] > 0.
- * Unknown space is not tracked: a voxel never seen is free, as in the reference.  There is no hit counting and no log-odds:
- * the last observation wins.  Both are out of scope.
+ * Unknown space does not enter the MAP: a voxel never seen is free there, as in the reference (what has been seen is recorded
+ * beside it on request: "known space and frontier goals" below).  There is no hit counting and no log-odds: the last
+ * observation wins.  Both are out of scope.
  * The walk.  All in double, no square root; inv = 1.0 / resolution and R2 = max_range * max_range computed once on the host;
  * e_a = (double)p_a, d_a = e_a - origin_a, dd = (d_x*d_x + d_y*d_y) + d_z*d_z without fused multiply-adds.  A ray is a HIT when
  * dd <= R2, otherwise TRUNCATED: it carves out to max_range and marks nothing.  Start voxel i: the origin's, by the DROP rule of
@@ -875,12 +877,13 @@ direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
 #define DIRECT_SCAN_RESET    0  /* the scan grid starts empty */
 #define DIRECT_SCAN_CONTINUE 1  /* keep it; a handle without one starts empty */
 #define DIRECT_SCAN_ADOPT    2  /* the scan grid starts as the bytes of the map the handle holds (INVALID without a map) */
+#define DIRECT_SCAN_TRACK_KNOWN 1  /* direct_map_scan_t.flags bit 0: record what this scan observed in the known grid (below) */
 typedef struct {
   double map_lower[3], map_upper[3];
   double resolution, max_range;
   double origin[3];
   int32_t inflate[3];
-  int32_t mode, stride /* 3 or 4 */, reserved;
+  int32_t mode, stride /* 3 or 4 */, flags /* DIRECT_SCAN_TRACK_KNOWN or 0; any other bit: DIRECT_ERR_INVALID, "unknown flags" */;
 } direct_map_scan_t;
 direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points,
                                                   int32_t mem, const float* xyz, int64_t* stats /* host [8] or NULL */);
@@ -890,6 +893,59 @@ direct_status_t direct_cluster_get_scan_grid(direct_cluster_handle_t h, int32_t 
  * changed) of the last scan.  Recorded only by a handle created with DIRECT_CLUSTER_SCAN_TIMING=1 in the environment
  * (DIRECT_ERR_INVALID otherwise); DIRECT_CLUSTER_SCAN_STORE=plain makes the carve store without loading the byte first. */
 direct_status_t direct_cluster_scan_phase_ms(direct_cluster_handle_t h, float* ms4);
+
+/* ---- known space and frontier goals ----------------------------------------------------------------------------------
+ * The KNOWN GRID is a third resident grid: the map's size and layout, one byte per voxel, 1 = observed, 0 = never observed.  It is
+ * allocated by the first call that needs it.  A scan with DIRECT_SCAN_TRACK_KNOWN in direct_map_scan_t.flags fills it from the
+ * walk it does anyway: every voxel the carve clears and every voxel the mark sets also gets known = 1 (a hit outside the map marks
+ * nothing).  Every writer writes 1, in both phases: the known grid depends neither on the order of the points nor on the launch
+ * shape.  With the flag, RESET empties the known grid too, CONTINUE and ADOPT keep it (a handle without one starts empty; ADOPT
+ * says nothing about what was seen - a caller with prior knowledge uses direct_cluster_set_known).  The scan grid, the map and
+ * the stats of a tracked scan are those of the same scan untracked.  A scan with flags == 0 is the call it has always been, and
+ * on a handle that holds a known grid it DROPS the grid: its rays were not recorded.  A tracked scan that fails on the device
+ * leaves no known grid.  direct_cluster_set_map and direct_cluster_map_from_cloud leave the known grid alone: it describes
+ * observation, not occupancy.
+ * direct_cluster_get_known: known[max_x*max_y*max_z] in memory kind `mem`; DIRECT_ERR_INVALID when the handle holds no known grid.
+ * direct_cluster_set_known: the handle's known grid becomes (known[v] != 0) of the caller's bytes, or all zero for known == NULL -
+ * a persisted grid, a declared-known box around the take-off point, a prior map.  It synchronises before it returns.
+ *
+ * direct_cluster_frontier turns map + known grid into a short ordered list of goal voxels, all integer and exact:
+ *   frontier voxel  known != 0, and enterable as the path calls see it (map byte 0 and, for min_d2 > 1, stored D2 >= min_d2: every
+ *                   frontier voxel is a legal goal of direct_cluster_grid_path_fan_batch under the same floor), and at least one of
+ *                   its 6 face neighbours INSIDE the map has known == 0.  The outside of the map is not unknown space.
+ *   component       a 26-connected component of the frontier voxels, labelled by its smallest linear index.
+ *   kept            size >= min_size.  The kept components in ascending label order fill the outputs; the first `capacity` are
+ *                   written.  stats[3] > capacity: call again with more room.
+ *   centroid        c_a = (2 * sum_a + n) / (2 * n) per axis (int64): the rounded mean of the members' coordinates.  It may be
+ *                   occupied, unknown or outside the component.
+ *   rep             the goal: the member that minimises (min(dist2, 0xffffffff) << 32) | linear index, dist2 = sum (v_a - c_a)^2:
+ *                   nearest the centroid voxel, ties to the smaller index.  Always known, enterable and on the frontier.
+ * stats: [0] known voxels, [1] frontier voxels, [2] components, [3] kept components, [4] written = min(kept, capacity), [5] the
+ * size of the largest component.  Entries of the per-component arrays from stats[4] on: -1 in host memory, untouched in device
+ * memory.  Any output may be NULL; capacity == 0 is a count-only call.
+ * DIRECT_ERR_INVALID, nothing launched, in this order: NULL handle, in or out; an unknown mem; min_d2 < 0, min_size < 1 or
+ * capacity < 0; capacity > 0 with label, size, centroid and rep all NULL; no map; no known grid; for min_d2 > 1, no valid distance
+ * field or min_d2 above its cap.  DIRECT_ERR_DEVICE: a device error, or the labelling's error word.
+ * The labelling is the union-find of direct_cluster_free_components on a mask grid, with buffers of this call's own: the
+ * resident free components are not touched and stay valid.  The call changes nothing else the handle holds, runs on the handle's
+ * stream and synchronises before it returns; direct_cluster_last_ms covers its clears and kernels.  Its workspace (13 B per voxel
+ * and 44 B per slot) and the staging of host outputs are blocks of its own on the handle, grown on demand, never shrunk and
+ * freed in direct_cluster_destroy; a handle that never calls it allocates nothing. */
+typedef struct { int32_t min_d2, min_size, capacity, mem; } direct_frontier_in_t;
+typedef struct {
+  int32_t* label;        /* [capacity]     smallest linear index of the component */
+  int32_t* size;         /* [capacity]     its voxel count */
+  int32_t* centroid;     /* [capacity][3]  rounded centroid voxel (may be occupied or unknown) */
+  int32_t* rep;          /* [capacity][3]  the goal: a voxel OF the component nearest the centroid voxel */
+  int32_t* voxel_label;  /* [G] or NULL    per voxel: its frontier component's label, -1 elsewhere */
+  int64_t* stats;        /* HOST [6] or NULL */
+} direct_frontier_out_t;
+direct_status_t direct_cluster_get_known(direct_cluster_handle_t h, int32_t mem, uint8_t* known);
+direct_status_t direct_cluster_set_known(direct_cluster_handle_t h, int32_t mem, const uint8_t* known /* or NULL: all zero */);
+direct_status_t direct_cluster_frontier(direct_cluster_handle_t h, const direct_frontier_in_t* in, const direct_frontier_out_t* out);
+/* For measurements: ms4[0..3] = HIP-event time [ms] of the mask, the labelling, the compaction and the goals (sums,
+ * representatives, unpack) of the last frontier call, recorded as direct_cluster_scan_phase_ms records (DIRECT_CLUSTER_SCAN_TIMING=1). */
+direct_status_t direct_cluster_frontier_phase_ms(direct_cluster_handle_t h, float* ms4);
 
 #ifdef __cplusplus
 }
