@@ -36,6 +36,16 @@ class FrontierOut(C.Structure):  # direct_frontier_out_t
                 ("stats", C.c_void_p)]
 
 
+class ViewGainIn(C.Structure):  # direct_view_gain_in_t
+    _fields_ = [("range_vox", C.c_double), ("n", C.c_int32), ("n_dirs", C.c_int32), ("n_sets", C.c_int32), ("mem_in", C.c_int32),
+                ("mem", C.c_int32)]
+
+
+class ViewGainIO(C.Structure):  # direct_view_gain_io_t
+    _fields_ = [("voxel", C.c_void_p), ("set", C.c_void_p), ("dirs", C.c_void_p), ("code", C.c_void_p), ("gain", C.c_void_p),
+                ("seen", C.c_void_p), ("ends", C.c_void_p)]
+
+
 class PlanCheckIn(C.Structure):  # direct_plan_check_in_t
     _fields_ = [("batch", C.c_int32), ("n_seg_max", C.c_int32), ("mem", C.c_int32), ("dtype", C.c_int32), ("n_seg", C.c_void_p),
                 ("T", C.c_void_p), ("bez", C.c_void_p), ("poly", C.c_void_p), ("map_lower", C.c_double * 3), ("resolution", C.c_double),
@@ -64,7 +74,7 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
            "direct_cluster_reachable_batch", "direct_cluster_corridor_batch", "direct_cluster_map_integrate_scan",
            "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms", "direct_cluster_get_known", "direct_cluster_set_known",
-           "direct_cluster_frontier", "direct_cluster_frontier_phase_ms")
+           "direct_cluster_frontier", "direct_cluster_frontier_phase_ms", "direct_cluster_view_gain_batch")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -72,6 +82,8 @@ MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
 SCAN_RESET, SCAN_CONTINUE, SCAN_ADOPT = 0, 1, 2
 SCAN_TRACK_KNOWN = 1   # direct_map_scan_t.flags
+VIEW_OK, VIEW_OUTSIDE, VIEW_OCCUPIED, VIEW_BAD_SET = 0, 1, 2, 3
+VIEW_ENDS = ("blocked", "left", "range", "skipped")   # ends[c][4]
 FRONTIER_STATS = ("known", "frontier", "components", "kept", "written", "largest")   # stats[6]
 SCAN_STATS = ("points", "skipped_nonfinite", "truncated", "outside", "raw_occupied", "occupied", "set", "cleared")   # stats[8]
 PLAN_CHECK_INVALID = -1
@@ -121,6 +133,7 @@ def _lib():
         L.direct_cluster_set_known.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_frontier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_frontier_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.direct_cluster_view_gain_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -133,6 +146,18 @@ def clearance_penalty_table(weight, soft_radius_vox):
     n = int(np.ceil(r * r)) if r > 0 else 0
     d2 = np.arange(n, dtype=np.float64)
     return float(weight) * (1.0 - np.sqrt(d2) / r) ** 2 if n else np.zeros(0, np.float64)
+
+
+def view_directions(n_az, n_el, el_min, el_max, az_min=-np.pi, az_max=np.pi, yaw=0.0):
+    """A direction set for view_gain: n_az x n_el unit vectors at the CENTRES of an even azimuth x elevation grid over
+    [az_min, az_max] x [el_min, el_max] (radians; elevation from the horizontal plane, positive up), turned by `yaw` about z.
+    Cell centres, so a full turn (the default azimuth span) has no doubled ray.  Built on the host with NumPy in float64 and
+    rounded once -> float32 [n_az * n_el][3], azimuth major.  Stack several (np.stack) to make the sets of one call."""
+    az = float(az_min) + (np.arange(int(n_az), dtype=np.float64) + 0.5) * ((float(az_max) - float(az_min)) / int(n_az)) + float(yaw)
+    el = float(el_min) + (np.arange(int(n_el), dtype=np.float64) + 0.5) * ((float(el_max) - float(el_min)) / int(n_el))
+    a, e = np.meshgrid(az, el, indexing="ij")
+    d = np.stack([np.cos(e) * np.cos(a), np.cos(e) * np.sin(a), np.sin(e)], axis=-1)
+    return np.ascontiguousarray(d.reshape(-1, 3), np.float32)
 
 
 def _check(st):
@@ -281,6 +306,50 @@ class ClusterGenerator:
         out["stats"] = dict(zip(FRONTIER_STATS, (int(v) for v in stats)))
         if voxel_labels:
             out["voxel_label"] = vox
+        return out
+
+    def view_gain(self, voxels, dirs, range_vox, sets=None, mem="host"):
+        """How much unknown space an ideal sensor would see from each candidate voxel (direct_cluster_view_gain_batch): the rays
+        of a direction set are walked from the centre of the voxel through the resident map, range_vox voxels far at most, until
+        they hit an occupied voxel or leave the map.  voxels [n][3] int32 (frontiers()["rep"], say); dirs [n_dirs][3] or
+        [n_sets][n_dirs][3] float32, map frame, any length (view_directions); sets [n] int32 or None (every candidate uses set 0):
+        NumPy arrays or device tensors.  voxels decides the kind: beside device voxels (frontiers(mem="device")["rep"]) host dirs
+        and sets are uploaded.  mem: where the outputs go ("host": NumPy, "device": tensors).
+        -> dict(code [n] (VIEW_*), gain [n]: distinct visited voxels with known == 0, seen [n]: distinct visited voxels,
+        ends [n][4]: rays that ended blocked, left the map, ran out of range, were skipped); a candidate whose code is not VIEW_OK
+        has zeros."""
+        assert mem in ("host", "device")
+        if isinstance(voxels, np.ndarray) or not hasattr(voxels, "data_ptr"):
+            vox = np.ascontiguousarray(voxels, np.int32).reshape(-1, 3)
+            d = np.ascontiguousarray(dirs, np.float32)
+            st = None if sets is None else np.ascontiguousarray(sets, np.int32).reshape(-1)
+            mem_in, ptr_in = abi.MEM_HOST, lambda a: a.ctypes.data
+        else:
+            import torch
+            vox = voxels.to(torch.int32).contiguous().reshape(-1, 3)
+            up = lambda a: a if hasattr(a, "data_ptr") else torch.as_tensor(np.asarray(a), device=vox.device)  # host arrays follow the voxels
+            d = up(dirs).to(torch.float32).contiguous()
+            st = None if sets is None else up(sets).to(torch.int32).contiguous().reshape(-1)
+            assert vox.is_cuda and d.is_cuda and (st is None or st.is_cuda)
+            torch.cuda.current_stream(vox.device).synchronize()  # the handle's stream is not torch's
+            mem_in, ptr_in = abi.MEM_DEVICE, lambda a: a.data_ptr()
+        d = d.reshape((1,) + tuple(d.shape)) if d.ndim == 2 else d
+        assert d.ndim == 3 and d.shape[2] == 3, "dirs must have shape [n_dirs, 3] or [n_sets, n_dirs, 3]"
+        n = int(vox.shape[0])
+        assert st is None or int(st.shape[0]) == n
+        shapes = dict(code=(n,), gain=(n,), seen=(n,), ends=(n, 4))
+        if mem == "host":
+            out = {k: np.zeros(s, np.int32) for k, s in shapes.items()}
+            ptr = lambda a: a.ctypes.data
+        else:
+            import torch
+            out = {k: torch.zeros(s, dtype=torch.int32, device="cuda:%d" % self.device) for k, s in shapes.items()}
+            torch.cuda.current_stream(out["code"].device).synchronize()  # the handle's stream is not torch's
+            ptr = lambda a: a.data_ptr()
+        par = ViewGainIn(float(range_vox), n, int(d.shape[1]), int(d.shape[0]), mem_in, abi.MEM_HOST if mem == "host" else abi.MEM_DEVICE)
+        io = ViewGainIO(ptr_in(vox) if n else None, None if st is None or not n else ptr_in(st), ptr_in(d),
+                        *[ptr(out[k]) if n else None for k in ("code", "gain", "seen", "ends")])
+        _check(_lib().direct_cluster_view_gain_batch(self.h, C.addressof(par), C.addressof(io)))
         return out
 
     def frontier_phase_ms(self):

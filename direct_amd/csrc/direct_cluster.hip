@@ -1000,6 +1000,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "cluster_corridor.h"
 #include "map_scan.h"
 #include "frontier.h"
+#include "view_gain.h"
 
 thread_local std::string g_cerr;
 direct_status_t cfail(direct_status_t st, const std::string& msg) {
@@ -1067,6 +1068,8 @@ struct direct_cluster_handle_s {
   hipEvent_t front_ev[5] = {};            // scan_timing: before the mask, behind the mask, the labelling, the compaction and the goals
   float front_ms[4] = {0, 0, 0, 0};
   bool front_timed = false;
+  hs::Block view_in, view_out;            // device staging of view_gain_batch's host inputs / its error word and host outputs, grown on demand
+  int view_threads = 0;                   // threads per workgroup of k_view_gain, 0: kViewThreads (DIRECT_CLUSTER_VIEW_THREADS: experiments)
 };
 
 namespace {
@@ -1505,6 +1508,7 @@ direct_status_t direct_cluster_create(const direct_cluster_config_t* cfg, direct
   if (const char* ev = getenv("DIRECT_CLUSTER_CONVEX_GRID")) h->convex_grid = atoi(ev) > 0 ? atoi(ev) : h->convex_grid;
   if (const char* ev = getenv("DIRECT_CLUSTER_SCAN_STORE")) h->scan_test_store = std::string(ev) != "plain";
   if (const char* ev = getenv("DIRECT_CLUSTER_SCAN_TIMING")) h->scan_timing = atoi(ev) > 0;
+  if (const char* ev = getenv("DIRECT_CLUSTER_VIEW_THREADS")) h->view_threads = (atoi(ev) == 256 || atoi(ev) == 512 || atoi(ev) == 1024) ? atoi(ev) : 0;
   if (const char* ev = getenv("DIRECT_CLUSTER_FAN_BOUND_EVERY")) h->fan_bound_every = atoi(ev) == gp::kFanRoundsPerCheck ? gp::kFanRoundsPerCheck : 1;
   Dev& D = h->D;
   D.max_x = cfg->max_x; D.max_y = cfg->max_y; D.max_z = cfg->max_z; D.max_yz = cfg->max_y * cfg->max_z;
@@ -1550,7 +1554,7 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
   for (void* p : h->allocs) (void)hipFree(p);
   for (hs::Block* b : {&h->hull_out, &h->path_out, &h->cloud_in, &h->plan_ws, &h->plan_io, &h->clear_ws, &h->clear_io, &h->cube_ws, &h->cube_in,
                        &h->cube_out, &h->fan_ws, &h->fan_out, &h->reach_in, &h->reach_out, &h->corr_ws, &h->corr_in, &h->corr_out, &h->scan_ws,
-                       &h->known_in, &h->front_ws, &h->front_out})
+                       &h->known_in, &h->front_ws, &h->front_out, &h->view_in, &h->view_out})
     hs::release(*b);
   for (hipEvent_t e : h->scan_ev)
     if (e) (void)hipEventDestroy(e);
@@ -2476,6 +2480,61 @@ direct_status_t direct_cluster_frontier_phase_ms(direct_cluster_handle_t h, floa
   if (!h || !ms4) return cfail(DIRECT_ERR_INVALID, "null argument");
   if (!h->scan_timing || !h->front_timed) return cfail(DIRECT_ERR_INVALID, "no timed frontier call: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
   for (int k = 0; k < 4; k++) ms4[k] = h->front_ms[k];
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_view_gain_batch(direct_cluster_handle_t h, const direct_view_gain_in_t* in, const direct_view_gain_io_t* io) {
+  if (!h || !in || !io) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(in->mem_in) || !mem_kind(in->mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (in->n < 0) return cfail(DIRECT_ERR_INVALID, "n must not be negative");
+  if (in->n_dirs < 1) return cfail(DIRECT_ERR_INVALID, "n_dirs must be at least 1");
+  if (in->n_sets < 1) return cfail(DIRECT_ERR_INVALID, "n_sets must be at least 1");
+  if (!std::isfinite(in->range_vox) || !(in->range_vox > 0.0)) return cfail(DIRECT_ERR_INVALID, "range_vox must be finite and positive");
+  if (in->n > 0 && (!io->voxel || !io->dirs)) return cfail(DIRECT_ERR_INVALID, "null voxel or dirs");
+  if (in->n > 0 && !io->code && !io->gain && !io->seen && !io->ends)
+    return cfail(DIRECT_ERR_INVALID, "no output: pass one of code, gain, seen, ends");
+  if (!vg::supported(in->range_vox))
+    return cfail(DIRECT_ERR_UNSUPPORTED, "range_vox: floor(range_vox) + 2 above " + std::to_string(vg::kMaxR) + ", the box of bits would not fit in LDS");
+  if (in->n_dirs > vg::kMaxDirs) return cfail(DIRECT_ERR_UNSUPPORTED, "n_dirs above " + std::to_string(vg::kMaxDirs));
+  if (!h->rs.has_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no map");
+  if (!h->rs.has_known()) return cfail(DIRECT_ERR_INVALID, "the handle has no known grid");
+  if (in->n == 0) return DIRECT_OK;
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t n = (size_t)in->n;
+  ViewDev V = {};
+  V.S.size[0] = h->D.max_x; V.S.size[1] = h->D.max_y; V.S.size[2] = h->D.max_z;
+  V.S.R = vg::box_half(in->range_vox);
+  V.S.R2 = in->range_vox * in->range_vox;
+  V.map = h->map; V.known = h->known;
+  V.n_dirs = in->n_dirs; V.n_sets = in->n_sets; V.words = vg::box_words(V.S.R);
+  hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(in->mem == DIRECT_MEM_HOST);
+  hs::stage_in(si, &V.voxel, io->voxel, n * 3 * sizeof(int32_t));
+  hs::stage_in(si, &V.set, io->set, n * sizeof(int32_t));
+  hs::stage_in(si, &V.dirs, io->dirs, (size_t)in->n_sets * in->n_dirs * 3 * sizeof(float));
+  hs::stage_scratch(so, &V.err, sizeof(unsigned int));
+  hs::stage_out(so, &V.code, io->code, n * sizeof(int32_t));
+  hs::stage_out(so, &V.gain, io->gain, n * sizeof(int32_t));
+  hs::stage_out(so, &V.seen, io->seen, n * sizeof(int32_t));
+  hs::stage_out(so, &V.ends, io->ends, n * 4 * sizeof(int32_t));
+  CHIP_TRY(hs::stage_upload(si, h->view_in, h->stream));
+  CHIP_TRY(hs::stage_upload(so, h->view_out, h->stream));
+  const size_t lds = (size_t)V.words * sizeof(unsigned int);
+  const int threads = h->view_threads ? h->view_threads : kViewThreads;
+  // the largest box is past the 64 KiB a launch gets without asking; a refusal here shows as the launch's own error
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_view_gain), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  (void)hipGetLastError();
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(V.err, 0, sizeof(unsigned int), h->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_view_gain, dim3((unsigned)n), dim3(threads), lds, h->stream, V);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  unsigned int err = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&err, V.err, sizeof(err), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, hs::stage_download(so, h->stream, e));
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("view_gain_batch: ") + hipGetErrorString(e));
+  if (err) return cfail(DIRECT_ERR_DEVICE, "view_gain_batch: a walk left its box or passed its trip bound (error word " + std::to_string(err) + ")");
   return DIRECT_OK;
 }
 

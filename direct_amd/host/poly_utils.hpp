@@ -26,6 +26,8 @@
 //     (direct_cluster_free_components, direct_cluster_reachable_batch)
 //   * integrateScan(..., track_known) / frontiers(min_size, min_d2, capacity) where the goals of a vehicle that maps as it flies
 //     come from: the boundary between what its scans have observed and what they have not (direct_cluster_frontier)
+//   * viewGain(voxels, dirs, n_sets, range_vox, sets) which of those goals is worth flying to: the unknown voxels an ideal sensor
+//     would see from each of them (direct_cluster_view_gain_batch)
 // Corridor / Polytope types are template parameters read through the member names of
 // global_planner/include/global_planner/utils/data_type.h:124-245 (polyhedrons, planes, center, seed_coord,
 // appendPlane, setSeed / setCenter where they exist); direct::PlainCorridor of ddp_optimizer.hpp fits.
@@ -138,6 +140,29 @@ class polyhedronGenerator {
     f.known = s[0]; f.frontier = s[1]; f.components = s[2]; f.kept = s[3]; f.written = s[4]; f.largest = s[5];
     f.label.resize((size_t)s[4]); f.size.resize((size_t)s[4]); f.centroid.resize((size_t)s[4]); f.rep.resize((size_t)s[4]);
     return f;
+  }
+  // How much unknown space an ideal sensor would see from each candidate voxel (direct_cluster_view_gain_batch): the rays of a
+  // direction set are walked from the centre of the voxel through the map the generator holds, range_vox voxels far at most, until
+  // they hit an occupied voxel or leave the map.  dirs holds n_sets sets of dirs.size() / n_sets directions each (map frame, any
+  // length); sets[c] says which one candidate c uses (nullptr: set 0).  gain[c]: distinct visited voxels the known grid does not
+  // hold; seen[c]: distinct visited voxels; ends[c]: rays blocked, left, out of range, skipped; code[c]: DIRECT_VIEW_*.
+  struct ViewGain {
+    std::vector<int32_t> code, gain, seen;     // [n]
+    std::vector<std::array<int32_t, 4>> ends;  // [n]
+  };
+  ViewGain viewGain(const std::vector<std::array<int32_t, 3>>& voxels, const std::vector<std::array<float, 3>>& dirs, int n_sets,
+                    double range_vox, const std::vector<int32_t>* sets = nullptr) {
+    if (n_sets < 1 || dirs.size() % (size_t)n_sets != 0) throw std::runtime_error("viewGain: dirs must hold n_sets sets of one size");
+    if (sets && sets->size() != voxels.size()) throw std::runtime_error("viewGain: one set index per voxel");
+    const size_t n = voxels.size();
+    ViewGain r;
+    r.code.resize(n); r.gain.resize(n); r.seen.resize(n); r.ends.resize(n);
+    const direct_view_gain_in_t in{range_vox, (int32_t)n, (int32_t)(dirs.size() / (size_t)n_sets), n_sets, DIRECT_MEM_HOST, DIRECT_MEM_HOST};
+    const direct_view_gain_io_t io{n ? &voxels[0][0] : nullptr, sets && n ? sets->data() : nullptr, dirs.empty() ? nullptr : &dirs[0][0],
+                                   n ? r.code.data() : nullptr, n ? r.gain.data() : nullptr, n ? r.seen.data() : nullptr,
+                                   n ? &r.ends[0][0] : nullptr};
+    if (direct_cluster_view_gain_batch(h_, &in, &io) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return r;
   }
   // the known grid as the generator holds it, [x][y][z] (direct_cluster_get_known); setKnown(nullptr) empties it
   std::vector<uint8_t> getKnown() {

@@ -947,6 +947,50 @@ direct_status_t direct_cluster_frontier(direct_cluster_handle_t h, const direct_
  * representatives, unpack) of the last frontier call, recorded as direct_cluster_scan_phase_ms records (DIRECT_CLUSTER_SCAN_TIMING=1). */
 direct_status_t direct_cluster_frontier_phase_ms(direct_cluster_handle_t h, float* ms4);
 
+/* ---- visible unknown volume per candidate viewpoint --------------------------------------------------------------------
+ * direct_cluster_view_gain_batch says which goal is worth flying to: for every candidate voxel v0 (direct_frontier_out_t.rep, say)
+ * it casts the rays of a direction set from the centre of v0 through the resident map and counts, all integer and exact,
+ *   seen     the DISTINCT voxels the rays pass,
+ *   gain     those of them with known == 0: the growth of the known grid if an ideal sensor with these rays scanned the map as it
+ *            stands from the centre of v0,
+ *   ends[4]  the rays by outcome: [0] blocked, [1] left the map, [2] out of range, [3] skipped.
+ * THE WALK of a direction dir (three floats, map frame, any length), in voxel units, double, no square root: d_a = (double)dir_a,
+ * dd = (d_x*d_x + d_y*d_y) + d_z*d_z, R2 = range_vox * range_vox.  The ray is SKIPPED when a component is not finite or dd == 0.
+ * step_a = sign(d_a); for step_a != 0, tdel_a = 1.0 / fabs(d_a) and tmax_a = 0.5 * tdel_a; i = v0.  Then, in this order: i outside
+ * the map ends the ray LEFT (i is not visited); i is visited; a map byte != 0 at i ends it BLOCKED (the voxel an ideal return would
+ * mark); c is the axis with the smallest tmax among those with step != 0, ties to the lower axis; t = tmax_c, and
+ * !((t*t)*dd <= R2) ends it out of RANGE; else i_c += step_c, tmax_c += tdel_c.  This is the carve walk of a truncated ray of
+ * direct_cluster_map_integrate_scan from a voxel centre, stopped at the first occupied voxel.  No offset from v0 exceeds
+ * floor(range_vox + 0.5) per axis.
+ * DIRECTION SETS: dirs holds n_sets sets of n_dirs directions, set[c] says which one candidate c uses (NULL: set 0) - several
+ * headings of a sensor with a limited field of view in one call, with no trigonometry on the device.
+ * code[c]: DIRECT_VIEW_OK; DIRECT_VIEW_OUTSIDE, the voxel is outside the map; DIRECT_VIEW_OCCUPIED, its map byte is != 0;
+ * DIRECT_VIEW_BAD_SET, set[c] is outside [0, n_sets) - checked in this order.  A candidate that is not OK gets zeros in gain, seen
+ * and ends and casts no ray.
+ * Refused, nothing launched and nothing written, in this order: a NULL handle, in or io; an unknown mem_in or mem; n < 0,
+ * n_dirs < 1, n_sets < 1; a range_vox that is not finite or <= 0; with n > 0, a NULL voxel or dirs, or code, gain, seen and ends
+ * all NULL (DIRECT_ERR_INVALID); floor(range_vox) + 2 > 50 or n_dirs > 65536 (DIRECT_ERR_UNSUPPORTED: the candidate's box of
+ * (2R+1)^3 bits, R = floor(range_vox) + 2, lives in LDS); no map; no known grid (DIRECT_ERR_INVALID).  n == 0 past these checks is
+ * DIRECT_OK.  DIRECT_ERR_DEVICE: a device error, or the kernel's error word (a walk outside its box or past its trip bound).
+ * The call reads the map and the known grid and changes nothing the handle holds.  voxel, set and dirs are read from memory kind
+ * mem_in, the outputs written to memory kind mem; device arrays are used in place.  It runs on the handle's stream and
+ * synchronises before it returns; direct_cluster_last_ms covers its kernel.  Its staging blocks are the handle's own, grown on
+ * demand, never shrunk and freed in direct_cluster_destroy.  For measurements: DIRECT_CLUSTER_VIEW_THREADS = 256, 512 or 1024 in
+ * the environment of direct_cluster_create sets the threads per workgroup (1024 otherwise; no output depends on it). */
+#define DIRECT_VIEW_OK 0
+#define DIRECT_VIEW_OUTSIDE 1
+#define DIRECT_VIEW_OCCUPIED 2
+#define DIRECT_VIEW_BAD_SET 3
+typedef struct { double range_vox; int32_t n, n_dirs, n_sets, mem_in, mem; } direct_view_gain_in_t;
+typedef struct {
+  const int32_t* voxel;   /* [n][3], e.g. direct_frontier_out_t.rep */
+  const int32_t* set;     /* [n] or NULL (all 0): which direction set each candidate uses */
+  const float*   dirs;    /* [n_sets][n_dirs][3], map frame, any length */
+  int32_t *code, *gain, *seen, *ends;   /* [n], [n], [n], [n][4]; any may be NULL, not all */
+} direct_view_gain_io_t;
+direct_status_t direct_cluster_view_gain_batch(direct_cluster_handle_t h, const direct_view_gain_in_t* in,
+                                               const direct_view_gain_io_t* io);
+
 #ifdef __cplusplus
 }
 #endif
