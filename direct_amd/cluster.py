@@ -27,6 +27,11 @@ class MapScan(C.Structure):  # direct_map_scan_t
                 ("flags", C.c_int32)]
 
 
+class MapEvidence(C.Structure):  # direct_map_evidence_t
+    _fields_ = [("scan", MapScan), ("hit", C.c_int32), ("miss", C.c_int32), ("ev_min", C.c_int32), ("ev_max", C.c_int32),
+                ("occ", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class FrontierIn(C.Structure):  # direct_frontier_in_t
     _fields_ = [("min_d2", C.c_int32), ("min_size", C.c_int32), ("capacity", C.c_int32), ("mem", C.c_int32)]
 
@@ -74,7 +79,9 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_cube_corridor_clear_batch", "direct_cluster_free_components", "direct_cluster_get_free_components",
            "direct_cluster_reachable_batch", "direct_cluster_corridor_batch", "direct_cluster_map_integrate_scan",
            "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms", "direct_cluster_get_known", "direct_cluster_set_known",
-           "direct_cluster_frontier", "direct_cluster_frontier_phase_ms", "direct_cluster_view_gain_batch")
+           "direct_cluster_frontier", "direct_cluster_frontier_phase_ms", "direct_cluster_view_gain_batch",
+           "direct_cluster_map_integrate_scan_evidence", "direct_cluster_get_evidence", "direct_cluster_set_evidence",
+           "direct_cluster_evidence_phase_ms")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -86,6 +93,7 @@ VIEW_OK, VIEW_OUTSIDE, VIEW_OCCUPIED, VIEW_BAD_SET = 0, 1, 2, 3
 VIEW_ENDS = ("blocked", "left", "range", "skipped")   # ends[c][4]
 FRONTIER_STATS = ("known", "frontier", "components", "kept", "written", "largest")   # stats[6]
 SCAN_STATS = ("points", "skipped_nonfinite", "truncated", "outside", "raw_occupied", "occupied", "set", "cleared")   # stats[8]
+EVIDENCE_STATS = SCAN_STATS + ("touched_hit", "touched_pass", "positive", "negative")   # stats[12]
 PLAN_CHECK_INVALID = -1
 DIST_NONE = 0x7fffffff
 CUBE_CORRIDOR_OK, CUBE_CORRIDOR_OVERFLOW, CUBE_CORRIDOR_BAD_PATH = 0, 1, 2
@@ -134,6 +142,10 @@ def _lib():
         L.direct_cluster_frontier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.direct_cluster_frontier_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
         L.direct_cluster_view_gain_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_map_integrate_scan_evidence.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.direct_cluster_get_evidence.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_set_evidence.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.direct_cluster_evidence_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
         _BOUND = True
     return L
 
@@ -275,6 +287,59 @@ class ClusterGenerator:
             mem, ptr = abi.MEM_DEVICE, known.data_ptr()
         assert known is None or tuple(known.shape) == self.dims
         _check(_lib().direct_cluster_set_known(self.h, mem, ptr))
+
+    def integrate_scan_evidence(self, points, origin, map_lower, resolution, max_range, hit=17, miss=8, ev_min=-40, ev_max=70, occ=1,
+                                inflate=(0, 0, 0), mode="continue", map_upper=None, track_known=False):
+        """One sensor scan folded into the resident EVIDENCE grid (direct_cluster_map_integrate_scan_evidence): every voxel a ray
+        passes loses `miss`, every voxel a return lies in gains `hit` (a return beats a pass), once per voxel and scan, clamped to
+        [ev_min, ev_max]; the scan grid is (evidence >= occ) and the map is the scan grid dilated by inflate.  The defaults are
+        OctoMap's 0.85 / -0.4 / [-2, 3.5] / 0 log-odds in units of 0.05.  points, origin, inflate, map_upper and track_known as in
+        integrate_scan.  mode: "reset" (the evidence starts at 0), "continue" (keep it) or "adopt" (ev_max where the map the handle
+        holds is occupied, 0 elsewhere).  No points and "continue": re-threshold the evidence as it stands.
+        -> dict of EVIDENCE_STATS: integrate_scan's eight, then touched_hit, touched_pass, positive, negative"""
+        lower = np.asarray(map_lower, np.float64).reshape(3)
+        upper = lower + np.asarray(self.dims, np.float64) * float(resolution) if map_upper is None else np.asarray(map_upper, np.float64).reshape(3)
+        pts, mem, ptr = self._cloud(points)
+        scan = MapScan((C.c_double * 3)(*lower), (C.c_double * 3)(*upper), float(resolution), float(max_range),
+                       (C.c_double * 3)(*np.asarray(origin, np.float64).reshape(3)), (C.c_int32 * 3)(*[int(v) for v in inflate]),
+                       {"reset": SCAN_RESET, "continue": SCAN_CONTINUE, "adopt": SCAN_ADOPT}[mode], int(pts.shape[1]),
+                       SCAN_TRACK_KNOWN if track_known else 0)
+        par = MapEvidence(scan, int(hit), int(miss), int(ev_min), int(ev_max), int(occ), (C.c_int32 * 3)(0, 0, 0))
+        n = int(pts.shape[0])
+        stats = np.zeros(12, np.int64)
+        _check(_lib().direct_cluster_map_integrate_scan_evidence(self.h, C.addressof(par), n, mem, ptr if n else None, stats.ctypes.data))
+        return dict(zip(EVIDENCE_STATS, (int(v) for v in stats)))
+
+    def evidence_grid(self):
+        """The evidence grid as an int8 array of shape dims (direct_cluster_get_evidence): what the evidence scans have counted per
+        voxel, 0 where nothing is known"""
+        g = np.zeros(self.dims, np.int8)
+        _check(_lib().direct_cluster_get_evidence(self.h, abi.MEM_HOST, g.ctypes.data))
+        return g
+
+    def set_evidence(self, ev):
+        """The evidence grid becomes a NumPy array or device tensor of shape dims, int8 (-128 is stored as -127); None: all zero
+        (direct_cluster_set_evidence).  Map and scan grid follow at the next integrate_scan_evidence."""
+        if ev is None:
+            mem, ptr = abi.MEM_HOST, None
+        elif isinstance(ev, np.ndarray) or not hasattr(ev, "data_ptr"):
+            ev = np.ascontiguousarray(ev, np.int8)
+            mem, ptr = abi.MEM_HOST, ev.ctypes.data
+        else:
+            import torch
+            ev = ev.to(torch.int8).contiguous()
+            assert ev.is_cuda
+            torch.cuda.current_stream(ev.device).synchronize()  # the handle's stream is not torch's
+            mem, ptr = abi.MEM_DEVICE, ev.data_ptr()
+        assert ev is None or tuple(ev.shape) == self.dims
+        _check(_lib().direct_cluster_set_evidence(self.h, mem, ptr))
+
+    def evidence_phase_ms(self):
+        """[touch, hit, fold, inflate, table] ms of the last evidence scan; the handle must have been created with
+        DIRECT_CLUSTER_SCAN_TIMING=1"""
+        ms = np.zeros(5, np.float32)
+        _check(_lib().direct_cluster_evidence_phase_ms(self.h, ms.ctypes.data))
+        return ms
 
     def frontiers(self, min_size=1, min_d2=0, capacity=1024, mem="host", voxel_labels=False):
         """Goal voxels on the boundary between observed and unobserved space (direct_cluster_frontier): the 26-connected components

@@ -999,6 +999,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "free_comp.h"
 #include "cluster_corridor.h"
 #include "map_scan.h"
+#include "map_evidence.h"
 #include "frontier.h"
 #include "view_gain.h"
 
@@ -1070,6 +1071,11 @@ struct direct_cluster_handle_s {
   bool front_timed = false;
   hs::Block view_in, view_out;            // device staging of view_gain_batch's host inputs / its error word and host outputs, grown on demand
   int view_threads = 0;                   // threads per workgroup of k_view_gain, 0: kViewThreads (DIRECT_CLUSTER_VIEW_THREADS: experiments)
+  int8_t* evid = nullptr;                 // the evidence grid (the map's size and layout), allocated by the first evidence scan or set_evidence
+  unsigned long long* evid_cnt = nullptr; // [kEvidCounters] the fold's counters
+  hipEvent_t evid_ev[6] = {};             // scan_timing: before the touch, behind the touch, the hit, the fold, the inflation and the table
+  float evid_ms[5] = {0, 0, 0, 0, 0};
+  bool evid_timed = false;
 };
 
 namespace {
@@ -1560,6 +1566,8 @@ direct_status_t direct_cluster_destroy(direct_cluster_handle_t h) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->front_ev)
     if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : h->evid_ev)
+    if (e) (void)hipEventDestroy(e);
   hs::destroy(h->ev);
   delete h;
   return DIRECT_OK;
@@ -1639,9 +1647,10 @@ direct_status_t direct_cluster_get_map(direct_cluster_handle_t h, int32_t mem, u
   return fetch_resident(h, mem, (size_t)h->D.G, map_data, h->map);
 }
 
-direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem,
-                                                  const float* xyz, int64_t* stats) {
-  if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+namespace {
+// map_integrate_scan and map_integrate_scan_evidence: everything both refuse of a scan behind their null check, in the plain call's
+// order and by its messages, the DIRECT_ERR_UNSUPPORTED ones included; S->G is the scan's geometry when nothing is refused
+direct_status_t scan_refusal(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem, const float* xyz, ScanDev* S) {
   const char* why = cloud_refusal(n_points, mem, xyz);
   if (!why && p->mode != DIRECT_SCAN_RESET && p->mode != DIRECT_SCAN_CONTINUE && p->mode != DIRECT_SCAN_ADOPT) why = "unknown mode";
   if (!why && !ms::flags_known(p->flags)) why = "unknown flags";
@@ -1654,8 +1663,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     if (p->inflate[a] < 0) return cfail(DIRECT_ERR_INVALID, "inflate must not be negative");
   }
   const Dev& D = h->D;
-  ScanDev S = {};
-  ms::Grid& G = S.G;
+  ms::Grid& G = S->G;
   G.resolution = p->resolution; G.inv = 1.0 / p->resolution; G.R2 = p->max_range * p->max_range;
   G.size[0] = D.max_x; G.size[1] = D.max_y; G.size[2] = D.max_z;
   for (int a = 0; a < 3; a++) {
@@ -1667,17 +1675,87 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   if (!(p->max_range * G.inv <= (double)ms::kMaxRangeVox)) return cfail(DIRECT_ERR_UNSUPPORTED, "max_range above 4096 voxels");
   for (int a = 0; a < 3; a++)
     if (p->inflate[a] > ms::kMaxInflate) return cfail(DIRECT_ERR_UNSUPPORTED, "inflate above 64 voxels");
-  CHIP_TRY(hipSetDevice(h->cfg.device));
-  const size_t cells = (size_t)D.G;
+  return DIRECT_OK;
+}
+
+// ... what both allocate behind their refusals (the scan grid and its counters, the known grid of a tracked scan, the dilation
+// workspace of at least `ws_cells` grids, the cloud on the device) ...
+direct_status_t scan_prepare(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem, const float* xyz,
+                             size_t ws_cells, ScanDev* S) {
+  const size_t cells = (size_t)h->D.G;
   if (!h->scan_raw)
     CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->scan_raw, cells), hs::want(&h->scan_cnt, kScanCounters * sizeof(unsigned long long))}));
   const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
   if (track && !h->known) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->known, cells)}));
+  S->n = n_points; S->stride = p->stride; S->raw = h->scan_raw; S->cnt = h->scan_cnt; S->known = track ? h->known : nullptr;
+  if (p->inflate[1] > 0 || p->inflate[2] > 0) ws_cells = std::max<size_t>(ws_cells, 2);
+  if (ws_cells > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, ws_cells * cells));
+  return cloud_on_device(h, n_points, p->stride, mem, xyz, &S->xyz);
+}
+
+// ... and the end of both, behind the kernels that wrote the scan grid: the dilation into the map with its counters, their
+// read-back (with `n_more` counters of the caller's own), the table where something changed, the state's events and stats[0..7].
+// `e` is what the call's enqueues have come to so far.  ev (null: untimed) are n_ev events, of which the caller has recorded all
+// but the last two, behind the inflation and behind the table; ms receives the n_ev - 1 times between them.
+direct_status_t scan_finish(direct_cluster_handle_t h, const direct_map_scan_t* p, const char* name, bool had_map, hipError_t e, hipEvent_t* ev,
+                            int n_ev, float* ms, int64_t n_points, int64_t* stats, const unsigned long long* more_dev, unsigned long long* more,
+                            int n_more) {
+  const size_t cells = (size_t)h->D.G;
+  const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
+  auto tick = [&](int k) { return ev ? hipEventRecord(ev[k], h->stream) : hipSuccess; };
+  if (e == hipSuccess) {  // z, then y, through the workspace where they inflate at all; x last, into the map
+    DilateDev P = {};
+    P.size[0] = h->D.max_x; P.size[1] = h->D.max_y; P.size[2] = h->D.max_z;
+    P.G = (long long)cells; P.cnt = h->scan_cnt; P.src = h->scan_raw;
+    const int blocks = (int)std::min<long long>(((long long)cells + 255) / 256, kScanMaxBlocks);
+    for (int axis = 2; axis >= 0; axis--) {
+      if (axis > 0 && p->inflate[axis] == 0) continue;
+      P.axis = axis; P.r = p->inflate[axis];
+      P.dst = axis == 0 ? h->map : (uint8_t*)h->scan_ws.p + (axis == 2 ? 0 : cells);
+      P.raw = axis == 0 ? h->scan_raw : nullptr;
+      hipLaunchKernelGGL(k_scan_dilate, dim3(blocks), dim3(256), 0, h->stream, P);
+      P.src = P.dst;
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(n_ev - 2);
+  unsigned long long cnt[kScanCounters] = {};
+  if (e == hipSuccess) e = hipMemcpyAsync(cnt, h->scan_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
+  if (e == hipSuccess && n_more > 0) e = hipMemcpyAsync(more, more_dev, n_more * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+  e = hs::drain(h->stream, e);
+  const bool changed = !had_map || cnt[kScanSet] + cnt[kScanCleared] > 0;
+  if (e == hipSuccess && changed) e = rebuild_sat(h);  // nothing changed: the table, the field, the floor tables and the labels stay
+  if (e == hipSuccess) e = tick(n_ev - 1);
+  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
+  e = hs::drain(h->stream, e);
+  if (e == hipSuccess && ev)
+    for (int k = 0; k < n_ev - 1 && e == hipSuccess; k++) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  if (e != hipSuccess) {  // the map and the scan grid have been touched: nothing describes them any more
+    h->rs.scan_ended(rs::ScanEnd::failed);
+    if (track) h->rs.known_ended(false);
+    return cfail(DIRECT_ERR_DEVICE, std::string(name) + ": " + hipGetErrorString(e));
+  }
+  h->rs.scan_ended(changed ? rs::ScanEnd::changed : rs::ScanEnd::unchanged);
+  if (track) h->rs.known_ended(true);
+  if (stats) {
+    stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
+    stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
+  }
+  return DIRECT_OK;
+}
+}  // namespace
+
+direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem,
+                                                  const float* xyz, int64_t* stats) {
+  if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+  ScanDev S = {};
+  if (const direct_status_t rc = scan_refusal(h, p, n_points, mem, xyz, &S)) return rc;
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->D.G;
+  const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
   if (h->scan_timing && !h->scan_ev[0])
     for (hipEvent_t& e : h->scan_ev) CHIP_TRY(hipEventCreate(&e));
-  S.n = n_points; S.stride = p->stride; S.raw = h->scan_raw; S.cnt = h->scan_cnt; S.known = track ? h->known : nullptr;
-  if (p->inflate[1] > 0 || p->inflate[2] > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, 2 * cells));
-  if (const direct_status_t rc = cloud_on_device(h, n_points, p->stride, mem, xyz, &S.xyz)) return rc;
+  if (const direct_status_t rc = scan_prepare(h, p, n_points, mem, xyz, 0, &S)) return rc;
   const bool had_map = h->rs.has_map();
   auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->scan_ev[k], h->stream) : hipSuccess; };
   CHIP_TRY(hs::start(h->ev, h->stream));
@@ -1691,6 +1769,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   h->rs.scan_began();  // no scan grid until the call has ended well
   if (track) h->rs.known_scan_began();  // ... and no known grid
   else h->rs.known_dropped();           // the rays of an untracked scan are not recorded: a known grid no longer describes what was seen
+  h->rs.evidence_dropped();             // the scan grid is written behind the evidence's back: an evidence grid no longer describes it
   const int ray_blocks = (int)std::min<long long>((n_points + 255) / 256, kScanMaxBlocks);
   if (e == hipSuccess) e = tick(0);
   if (e == hipSuccess && n_points > 0) {
@@ -1705,43 +1784,112 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = tick(2);
-  if (e == hipSuccess) {  // z, then y, through the workspace where they inflate at all; x last, into the map
-    DilateDev P = {};
-    for (int a = 0; a < 3; a++) P.size[a] = G.size[a];
-    P.G = (long long)cells; P.cnt = h->scan_cnt; P.src = h->scan_raw;
-    const int blocks = (int)std::min<long long>(((long long)cells + 255) / 256, kScanMaxBlocks);
-    for (int axis = 2; axis >= 0; axis--) {
-      if (axis > 0 && p->inflate[axis] == 0) continue;
-      P.axis = axis; P.r = p->inflate[axis];
-      P.dst = axis == 0 ? h->map : (uint8_t*)h->scan_ws.p + (axis == 2 ? 0 : cells);
-      P.raw = axis == 0 ? h->scan_raw : nullptr;
-      hipLaunchKernelGGL(k_scan_dilate, dim3(blocks), dim3(256), 0, h->stream, P);
-      P.src = P.dst;
-    }
+  return scan_finish(h, p, "map_integrate_scan", had_map, e, h->scan_timing ? h->scan_ev : nullptr, 5, h->scan_ms, n_points, stats, nullptr, nullptr, 0);
+}
+
+direct_status_t direct_cluster_map_integrate_scan_evidence(direct_cluster_handle_t h, const direct_map_evidence_t* p, int64_t n_points,
+                                                           int32_t mem, const float* xyz, int64_t* stats) {
+  if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
+  const direct_map_scan_t* sp = &p->scan;
+  ScanDev S = {};
+  if (const direct_status_t rc = scan_refusal(h, sp, n_points, mem, xyz, &S)) return rc;
+  EvidDev E = {};
+  E.P.hit = p->hit; E.P.miss = p->miss; E.P.ev_min = p->ev_min; E.P.ev_max = p->ev_max; E.P.occ = p->occ;
+  if (const char* why = me::refusal(E.P, p->reserved)) return cfail(DIRECT_ERR_INVALID, why);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->D.G;
+  const bool track = (sp->flags & DIRECT_SCAN_TRACK_KNOWN) != 0, adopt = sp->mode == DIRECT_SCAN_ADOPT;
+  if (!h->evid) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->evid, cells), hs::want(&h->evid_cnt, kEvidCounters * sizeof(unsigned long long))}));
+  if (h->scan_timing && !h->evid_ev[0])
+    for (hipEvent_t& e : h->evid_ev) CHIP_TRY(hipEventCreate(&e));
+  if (const direct_status_t rc = scan_prepare(h, sp, n_points, mem, xyz, 1, &S)) return rc;  // the touch grid: the workspace's first grid
+  uint8_t* touch = (uint8_t*)h->scan_ws.p;
+  E.G = (long long)cells; E.touch = touch; E.ev = h->evid; E.map = adopt ? h->map : nullptr; E.raw = h->scan_raw; E.known = S.known; E.cnt = h->evid_cnt;
+  const bool had_map = h->rs.has_map();
+  auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->evid_ev[k], h->stream) : hipSuccess; };
+  CHIP_TRY(hs::start(h->ev, h->stream));
+  hipError_t e = hipMemsetAsync(h->scan_cnt, 0, kScanCounters * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(h->evid_cnt, 0, kEvidCounters * sizeof(unsigned long long), h->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(touch, 0, cells, h->stream);
+  if (e == hipSuccess && !had_map) e = hipMemsetAsync(h->map, 0, cells, h->stream);  // the bytes "before" of a handle without a map
+  // the fold compares before it stores: what it compares with has to be defined.  ADOPT takes the map's bytes and stores always.
+  if (e == hipSuccess && !adopt && (sp->mode == DIRECT_SCAN_RESET || !h->rs.has_evidence())) e = hipMemsetAsync(h->evid, 0, cells, h->stream);
+  if (e == hipSuccess && !h->rs.has_scan_grid()) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
+  if (e == hipSuccess && track && (sp->mode == DIRECT_SCAN_RESET || !h->rs.has_known())) e = hipMemsetAsync(h->known, 0, cells, h->stream);
+  h->rs.scan_began();           // no scan grid until the call has ended well
+  h->rs.evidence_scan_began();  // ... no evidence grid
+  if (track) h->rs.known_scan_began();  // ... and no known grid
+  else h->rs.known_dropped();           // the rays of an untracked scan are not recorded, as in the plain call
+  const int ray_blocks = (int)std::min<long long>((n_points + 255) / 256, kScanMaxBlocks);
+  if (e == hipSuccess) e = tick(0);
+  if (e == hipSuccess && n_points > 0) {
+    hipLaunchKernelGGL(h->scan_test_store ? k_evid_touch<true> : k_evid_touch<false>, dim3(ray_blocks), dim3(256), 0, h->stream, S, touch);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(1);
+  if (e == hipSuccess && n_points > 0) {
+    hipLaunchKernelGGL(k_evid_hit, dim3(ray_blocks), dim3(256), 0, h->stream, S, touch);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = tick(2);
+  if (e == hipSuccess) {
+    const long long groups = ((long long)cells + kEvidGroup - 1) / kEvidGroup;
+    const int blocks = (int)std::min<long long>((groups + 255) / 256, kScanMaxBlocks);
+    auto fold = adopt ? (track ? k_evid_fold<true, true> : k_evid_fold<true, false>) : (track ? k_evid_fold<false, true> : k_evid_fold<false, false>);
+    hipLaunchKernelGGL(fold, dim3(blocks), dim3(256), 0, h->stream, E);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = tick(3);
-  unsigned long long cnt[kScanCounters] = {};
-  if (e == hipSuccess) e = hipMemcpyAsync(cnt, h->scan_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
-  e = hs::drain(h->stream, e);
-  const bool changed = !had_map || cnt[kScanSet] + cnt[kScanCleared] > 0;
-  if (e == hipSuccess && changed) e = rebuild_sat(h);  // nothing changed: the table, the field, the floor tables and the labels stay
-  if (e == hipSuccess) e = tick(4);
-  if (e == hipSuccess) e = hs::stop(h->ev, h->stream);
-  e = hs::drain(h->stream, e);
-  if (e == hipSuccess && h->scan_timing)
-    for (int k = 0; k < 4 && e == hipSuccess; k++) e = hipEventElapsedTime(&h->scan_ms[k], h->scan_ev[k], h->scan_ev[k + 1]);
-  if (e != hipSuccess) {  // the map and the scan grid have been touched: nothing describes them any more
-    h->rs.scan_ended(rs::ScanEnd::failed);
-    if (track) h->rs.known_ended(false);
-    return cfail(DIRECT_ERR_DEVICE, std::string("map_integrate_scan: ") + hipGetErrorString(e));
+  unsigned long long more[kEvidCounters] = {};
+  const direct_status_t rc = scan_finish(h, sp, "map_integrate_scan_evidence", had_map, e, h->scan_timing ? h->evid_ev : nullptr, 6, h->evid_ms,
+                                         n_points, stats, h->evid_cnt, more, kEvidCounters);
+  h->rs.evidence_ended(rc == DIRECT_OK);
+  h->evid_timed = h->scan_timing && rc == DIRECT_OK;
+  if (rc == DIRECT_OK && stats)
+    for (int k = 0; k < kEvidCounters; k++) stats[8 + k] = (int64_t)more[k];
+  return rc;
+}
+
+direct_status_t direct_cluster_get_evidence(direct_cluster_handle_t h, int32_t mem, int8_t* ev) {
+  if (!h || !ev) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_evidence()) return cfail(DIRECT_ERR_INVALID, "the handle has no evidence grid");
+  return fetch_resident(h, mem, (size_t)h->D.G, ev, h->evid);
+}
+
+direct_status_t direct_cluster_set_evidence(direct_cluster_handle_t h, int32_t mem, const int8_t* ev) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  CHIP_TRY(hipSetDevice(h->cfg.device));
+  const size_t cells = (size_t)h->D.G;
+  if (!h->evid) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->evid, cells), hs::want(&h->evid_cnt, kEvidCounters * sizeof(unsigned long long))}));
+  const int8_t* src = ev;
+  if (ev && mem == DIRECT_MEM_HOST) {
+    CHIP_TRY(hs::grow(h->known_in, h->stream, cells));  // the staging of set_known's host bytes serves both: each call drains
+    src = (const int8_t*)h->known_in.p;
   }
-  h->rs.scan_ended(changed ? rs::ScanEnd::changed : rs::ScanEnd::unchanged);
-  if (track) h->rs.known_ended(true);
-  if (stats) {
-    stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
-    stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
+  h->rs.evidence_dropped();  // the grid is about to be written: not present until the call has drained
+  hipError_t e = hipSuccess;
+  if (!ev) {
+    e = hipMemsetAsync(h->evid, 0, cells, h->stream);
+  } else {
+    if (mem == DIRECT_MEM_HOST) e = hipMemcpyAsync(h->known_in.p, ev, cells, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+      const int blocks = (int)std::min<long long>(((long long)cells + 255) / 256, kScanMaxBlocks);
+      hipLaunchKernelGGL(k_evid_set, dim3(blocks), dim3(256), 0, h->stream, h->evid, src, (long long)cells);
+      e = hipGetLastError();
+    }
   }
+  e = hs::drain(h->stream, e);
+  if (e != hipSuccess) return cfail(DIRECT_ERR_DEVICE, std::string("set_evidence: ") + hipGetErrorString(e));
+  h->rs.evidence_set();
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_evidence_phase_ms(direct_cluster_handle_t h, float* ms5) {
+  if (!h || !ms5) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!h->scan_timing || !h->evid_timed) return cfail(DIRECT_ERR_INVALID, "no timed evidence scan: set DIRECT_CLUSTER_SCAN_TIMING=1 before direct_cluster_create");
+  for (int k = 0; k < 5; k++) ms5[k] = h->evid_ms[k];
   return DIRECT_OK;
 }
 

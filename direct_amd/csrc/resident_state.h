@@ -6,7 +6,7 @@
 //
 // Two properties the C boundary depends on:
 //   - All-zero bytes mean "nothing resident": every question answers from a zeroed object (no map, no valid field, no valid
-//     labels, no scan grid, no known grid, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer
+//     labels, no scan grid, no known grid, no evidence grid, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer
 //     as a handle and assert that a refused call wrote not one byte of it.
 //   - No pointers, trivially copyable, a few dozen bytes.
 //
@@ -58,6 +58,15 @@ struct State {
   void known_set() { have_known_ = 1; }             // set_known has drained: the caller's bytes, or all zero
   void known_dropped() { have_known_ = 0; }         // an untracked scan past its refusals (its rays were not recorded), a failed set_known
   bool has_known() const { return have_known_ != 0; }
+
+  // ---- the evidence grid (what the evidence scans have counted per voxel; like the known grid it describes observation: no
+  // map event touches it, and neither frontier nor view_gain_batch does)
+  void evidence_scan_began() { have_evid_ = 0; }     // an evidence scan folds into it: not present until the call has ended well
+  void evidence_ended(bool ok) { have_evid_ = ok; }  // ... which a device error does not
+  void evidence_set() { have_evid_ = 1; }            // set_evidence has drained: the caller's bytes, or all zero
+  // a PLAIN scan past its refusals (it writes the scan grid behind the evidence's back), a failed set_evidence
+  void evidence_dropped() { have_evid_ = 0; }
+  bool has_evidence() const { return have_evid_ != 0; }
 
   // ---- the distance field ------------------------------------------------------------------------------------------------
   void field_call_began() { field_gen_++; }    // every distance_field past its null check: labels built with a floor are stale
@@ -112,6 +121,7 @@ struct State {
   freecomp::Key label_key_;              // what the labels were built from (valid == 0: none)
   int32_t clusters_;
   int32_t have_known_;
+  int32_t have_evid_;
 };
 static_assert(std::is_trivially_copyable<State>::value && std::is_standard_layout<State>::value, "plain data: zero bytes are a State");
 static_assert(sizeof(State) <= 256, "a handle is far smaller than the 64 KiB the ABI tests hand over");

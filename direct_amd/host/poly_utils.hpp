@@ -119,6 +119,55 @@ class polyhedronGenerator {
     r.raw_occupied = s[4]; r.occupied = s[5]; r.set = s[6]; r.cleared = s[7];
     return r;
   }
+  // One sensor scan folded into the resident EVIDENCE grid (direct_cluster_map_integrate_scan_evidence), for a sensor that is
+  // sometimes wrong: every voxel a ray passes loses `miss`, every voxel a return lies in gains `hit` (a return beats a pass), once
+  // per voxel and scan, clamped to [ev_min, ev_max]; the scan grid is (evidence >= occ) and the map is the scan grid dilated by
+  // inflate.  The defaults are OctoMap's 0.85 / -0.4 / [-2, 3.5] / 0 log-odds in units of 0.05.  mode as in integrateScan (ADOPT:
+  // ev_max where the map is occupied).  n == 0 with DIRECT_SCAN_CONTINUE re-thresholds the evidence as it stands.  A plain
+  // integrateScan drops the evidence grid; setMap and setCloud keep it.
+  struct EvidenceParams {
+    int hit, miss, ev_min, ev_max, occ;
+    EvidenceParams() : hit(17), miss(8), ev_min(-40), ev_max(70), occ(1) {}
+  };
+  struct EvidenceResult : ScanResult {
+    long long touched_hit = 0, touched_pass = 0, positive = 0, negative = 0;
+  };
+  EvidenceResult integrateScanEvidence(const float* xyz, int64_t n, int stride, const std::array<double, 3>& origin, double max_range,
+                                       const EvidenceParams& ev = EvidenceParams(), const std::array<int, 3>& inflate = {{0, 0, 0}},
+                                       int mode = DIRECT_SCAN_CONTINUE, bool track_known = false) {
+    direct_map_evidence_t p{};
+    for (int a = 0; a < 3; a++) {
+      p.scan.map_lower[a] = lower_[a];
+      p.scan.map_upper[a] = lower_[a] + (a == 0 ? mx_ : (a == 1 ? my_ : mz_)) * res_;
+      p.scan.origin[a] = origin[a];
+      p.scan.inflate[a] = inflate[a];
+    }
+    p.scan.resolution = res_;
+    p.scan.max_range = max_range;
+    p.scan.mode = mode;
+    p.scan.stride = stride;
+    p.scan.flags = track_known ? DIRECT_SCAN_TRACK_KNOWN : 0;
+    p.hit = ev.hit; p.miss = ev.miss; p.ev_min = ev.ev_min; p.ev_max = ev.ev_max; p.occ = ev.occ;
+    int64_t s[12];
+    if (direct_cluster_map_integrate_scan_evidence(h_, &p, n, DIRECT_MEM_HOST, xyz, s) != DIRECT_OK)
+      throw std::runtime_error(direct_cluster_last_error());
+    has_map_ = true;
+    EvidenceResult r;
+    r.points = s[0]; r.skipped_nonfinite = s[1]; r.truncated = s[2]; r.outside = s[3];
+    r.raw_occupied = s[4]; r.occupied = s[5]; r.set = s[6]; r.cleared = s[7];
+    r.touched_hit = s[8]; r.touched_pass = s[9]; r.positive = s[10]; r.negative = s[11];
+    return r;
+  }
+  // the evidence grid as the generator holds it, [x][y][z] (direct_cluster_get_evidence); setEvidence(nullptr) empties it.  Map
+  // and scan grid follow at the next integrateScanEvidence.
+  std::vector<int8_t> evidence() {
+    std::vector<int8_t> m((size_t)mx_ * my_ * mz_);
+    if (direct_cluster_get_evidence(h_, DIRECT_MEM_HOST, m.data()) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return m;
+  }
+  void setEvidence(const int8_t* ev) {
+    if (direct_cluster_set_evidence(h_, DIRECT_MEM_HOST, ev) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+  }
   // Goal voxels on the boundary between observed and unobserved space (direct_cluster_frontier): the 26-connected components of
   // the known, enterable voxels with an unknown face neighbour inside the map; those of at least min_size voxels in ascending
   // label order, the first `capacity` of them.  rep[k] is a member of component k - known, enterable under the floor min_d2 - and

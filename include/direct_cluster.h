@@ -850,8 +850,10 @@ direct_status_t direct_cluster_last_ms(direct_cluster_handle_t h, float* ms);
  *               NOTHING changed, all of them stay valid and nothing is rebuilt: a node that scans a static room at 10 Hz pays
  *               for no field.  Rebuild the field when stats[6] + stats[7] > 0.
  * Unknown space does not enter the MAP: a voxel never seen is free there, as in the reference (what has been seen is recorded
- * beside it on request: "known space and frontier goals" below).  There is no hit counting and no log-odds: the last
- * observation wins.  Both are out of scope.
+ * beside it on request: "known space and frontier goals" below).  THIS call counts no hits and keeps no log-odds: the last
+ * observation wins.  Evidence per voxel lives in a call of its own, direct_cluster_map_integrate_scan_evidence ("occupancy
+ * evidence per voxel" below), which derives the scan grid and the map from a resident evidence grid; a plain scan past its
+ * refusals writes the scan grid behind that grid's back and therefore drops it.
  * The walk.  All in double, no square root; inv = 1.0 / resolution and R2 = max_range * max_range computed once on the host;
  * e_a = (double)p_a, d_a = e_a - origin_a, dd = (d_x*d_x + d_y*d_y) + d_z*d_z without fused multiply-adds.  A ray is a HIT when
  * dd <= R2, otherwise TRUNCATED: it carves out to max_range and marks nothing.  Start voxel i: the origin's, by the DROP rule of
@@ -946,6 +948,60 @@ direct_status_t direct_cluster_frontier(direct_cluster_handle_t h, const direct_
 /* For measurements: ms4[0..3] = HIP-event time [ms] of the mask, the labelling, the compaction and the goals (sums,
  * representatives, unpack) of the last frontier call, recorded as direct_cluster_scan_phase_ms records (DIRECT_CLUSTER_SCAN_TIMING=1). */
 direct_status_t direct_cluster_frontier_phase_ms(direct_cluster_handle_t h, float* ms4);
+
+/* ---- occupancy evidence per voxel: scans that count hits and misses ---------------------------------------------------
+ * direct_cluster_map_integrate_scan lets the last observation win: one spurious return occupies a voxel, one grazing ray erases a
+ * thin obstacle.  This call accumulates instead, in the manner of clamped log-odds with one update per voxel and scan, in
+ * integers: the result is exactly defined and depends neither on the order of the points nor on the launch shape.  It is restated
+ * by tests/evidence_harness.py.  There is no reference counterpart.
+ * The EVIDENCE GRID is a further resident grid: the map's size and layout, one int8 per voxel, 0 = no information, allocated by
+ * the first call that needs it.  `scan` (geometry, inflate, mode, stride, flags) is read exactly as the plain call reads it.
+ * One call is one scan, five steps in order on the handle's stream:
+ *   0. Start    RESET: ev = 0 everywhere (with DIRECT_SCAN_TRACK_KNOWN the known grid is emptied too, as in the plain call).
+ *               CONTINUE: keep ev; a handle without an evidence grid starts from zeros.  ADOPT: ev[v] = (map[v] == 1) ? ev_max : 0
+ *               (DIRECT_ERR_INVALID without a map, as in the plain call).
+ *   1. Touch    a per-call touch grid starts at 0; every ray writes 1 into exactly the voxels the plain scan's carve would clear
+ *               (the same walk).
+ *   2. Hit      every HIT ray whose voxel is inside the map writes 2 into the touch byte of that voxel.  All of step 1 precedes
+ *               all of step 2 and each phase writes one value: a voxel both passed and hit in one scan is a hit.
+ *   3. Fold     once per voxel, in int arithmetic with t = touch[v] and e = ev[v]:  t == 2: e = min(e + hit, ev_max);
+ *               t == 1: e = max(e - miss, ev_min);  t == 0: e is unchanged, even where it lies outside this call's clamp (an
+ *               earlier call with other limits, or set_evidence, may have left it there).  Then ev[v] = e and
+ *               raw[v] = (e >= occ) for EVERY voxel, touched or not: behind every evidence scan the scan grid is a function of
+ *               the evidence grid and occ alone, and whatever a plain scan left in it is overwritten.  With
+ *               DIRECT_SCAN_TRACK_KNOWN known[v] |= (t != 0); with flags == 0 a known grid the handle holds is dropped, as the
+ *               plain call drops it.
+ *   4. Inflate and tables: steps 3 and 4 of the plain call, on the same code - raw dilated into the map, 0 -> 1 and 1 -> 0
+ *               counted against the bytes the map held, the table rebuilt and the field, floor tables and components stale ONLY
+ *               if something changed or the handle had no map.
+ * n_points == 0 is legal; with CONTINUE it re-thresholds: after set_evidence, or with another occ, it derives scan grid and map
+ * from the evidence alone.
+ * stats (host [12], may be NULL): [0..7] as in the plain call; [8] voxels touched as hit, [9] voxels touched as pass only,
+ * [10] voxels with ev > 0 after the call, [11] voxels with ev < 0 after the call.
+ * Refused, the handle left as it was: first everything the plain call refuses, in its order and by its messages (the
+ * DIRECT_ERR_UNSUPPORTED ones included); then DIRECT_ERR_INVALID for hit, miss, ev_min, ev_max, occ, reserved, in this order, each
+ * by a message that names the field.  After DIRECT_ERR_DEVICE the handle has no map, no scan grid and no evidence grid, and a
+ * tracked scan leaves no known grid.
+ * direct_cluster_set_map and direct_cluster_map_from_cloud leave the evidence grid alone (it describes observation: the next
+ * CONTINUE evidence scan derives the map again and counts its changes against the bytes it finds); direct_cluster_frontier and
+ * direct_cluster_view_gain_batch do not touch it.
+ * direct_cluster_get_evidence: ev[max_x*max_y*max_z] in memory kind `mem`; DIRECT_ERR_INVALID when the handle holds no evidence grid.
+ * direct_cluster_set_evidence: the evidence grid becomes max(ev[v], -127) of the caller's bytes, or all zero for ev == NULL.  It
+ * synchronises before it returns and touches neither the map nor the scan grid: they follow at the next evidence scan.
+ * direct_cluster_evidence_phase_ms: ms5[0..4] = HIP-event time [ms] of the touch, the hit, the fold, the inflation and the table
+ * rebuild (0 when nothing changed) of the last evidence scan, recorded as direct_cluster_scan_phase_ms records. */
+typedef struct {
+  direct_map_scan_t scan;   /* geometry, inflate, mode, stride, flags: exactly as for direct_cluster_map_integrate_scan */
+  int32_t hit, miss;        /* added for a return / subtracted for a pass, 1 .. 127 each */
+  int32_t ev_min, ev_max;   /* clamp of a TOUCHED voxel: -127 <= ev_min <= 0, occ <= ev_max <= 127 */
+  int32_t occ;              /* a voxel is occupied when ev >= occ; 1 <= occ <= ev_max */
+  int32_t reserved[3];      /* must be 0 */
+} direct_map_evidence_t;    /* 112 + 32 = 144 bytes */
+direct_status_t direct_cluster_map_integrate_scan_evidence(direct_cluster_handle_t h, const direct_map_evidence_t* p, int64_t n_points,
+                                                           int32_t mem, const float* xyz, int64_t* stats /* host [12] or NULL */);
+direct_status_t direct_cluster_get_evidence(direct_cluster_handle_t h, int32_t mem, int8_t* ev);
+direct_status_t direct_cluster_set_evidence(direct_cluster_handle_t h, int32_t mem, const int8_t* ev /* or NULL: all zero */);
+direct_status_t direct_cluster_evidence_phase_ms(direct_cluster_handle_t h, float* ms5);
 
 /* ---- visible unknown volume per candidate viewpoint --------------------------------------------------------------------
  * direct_cluster_view_gain_batch says which goal is worth flying to: for every candidate voxel v0 (direct_frontier_out_t.rep, say)
