@@ -81,7 +81,8 @@ EXPORTS = ("direct_cluster_create", "direct_cluster_destroy", "direct_cluster_la
            "direct_cluster_get_scan_grid", "direct_cluster_scan_phase_ms", "direct_cluster_get_known", "direct_cluster_set_known",
            "direct_cluster_frontier", "direct_cluster_frontier_phase_ms", "direct_cluster_view_gain_batch",
            "direct_cluster_map_integrate_scan_evidence", "direct_cluster_get_evidence", "direct_cluster_set_evidence",
-           "direct_cluster_evidence_phase_ms")
+           "direct_cluster_evidence_phase_ms", "direct_cluster_set_unknown_policy", "direct_cluster_get_unknown_policy",
+           "direct_cluster_get_open_map")
 CLUSTER_OK, CLUSTER_OVERFLOW, CLUSTER_BAD_SEED = 0, 1, 2
 HULL_OK, HULL_OVERFLOW, HULL_BAD_VOXEL, HULL_FLAT = 0, 1, 2, 3
 GRID_PATH_OK, GRID_PATH_NO_PATH, GRID_PATH_BAD_ENDPOINT, GRID_PATH_OVERFLOW, GRID_PATH_ROUND_LIMIT = 0, 1, 2, 3, 4
@@ -89,6 +90,8 @@ MAP_BORDER_CLAMP, MAP_BORDER_DROP = 0, 1
 MAP_REPLACE, MAP_ADD = 0, 1
 SCAN_RESET, SCAN_CONTINUE, SCAN_ADOPT = 0, 1, 2
 SCAN_TRACK_KNOWN = 1   # direct_map_scan_t.flags
+UNKNOWN_FREE, UNKNOWN_OCCUPIED = 0, 1
+UNKNOWN_POLICIES = ("free", "occupied")   # by value
 VIEW_OK, VIEW_OUTSIDE, VIEW_OCCUPIED, VIEW_BAD_SET = 0, 1, 2, 3
 VIEW_ENDS = ("blocked", "left", "range", "skipped")   # ends[c][4]
 FRONTIER_STATS = ("known", "frontier", "components", "kept", "written", "largest")   # stats[6]
@@ -146,6 +149,9 @@ def _lib():
         L.direct_cluster_get_evidence.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_set_evidence.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.direct_cluster_evidence_phase_ms.argtypes = [C.c_void_p, C.c_void_p]
+        L.direct_cluster_set_unknown_policy.argtypes = [C.c_void_p, C.c_int32]
+        L.direct_cluster_get_unknown_policy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.direct_cluster_get_open_map.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         _BOUND = True
     return L
 
@@ -340,6 +346,28 @@ class ClusterGenerator:
         ms = np.zeros(5, np.float32)
         _check(_lib().direct_cluster_evidence_phase_ms(self.h, ms.ctypes.data))
         return ms
+
+    def set_unknown_policy(self, policy):
+        """What the scans make of voxels nobody has observed (direct_cluster_set_unknown_policy): "free" (the default: their map
+        byte is 0) or "occupied" (every scan keeps two grids: the open map, which is what it derives under "free", and the map,
+        which is the open map with every unobserved voxel closed; every planning call reads the map, view_gain the open map).
+        Takes effect at the next scan, which must be tracked under "occupied"; touches no grid."""
+        _check(_lib().direct_cluster_set_unknown_policy(self.h, UNKNOWN_POLICIES.index(policy)))
+
+    def unknown_policy(self):
+        """-> dict(policy: "free" or "occupied", closed: voxels occupied in the map and free in the open map, open_ones: occupied
+        voxels of the open map), the counts of the last successful scan under "occupied" (0 when the handle holds no open map)"""
+        policy = C.c_int32(-1)
+        stats = np.zeros(2, np.int64)
+        _check(_lib().direct_cluster_get_unknown_policy(self.h, C.addressof(policy), stats.ctypes.data))
+        return dict(policy=UNKNOWN_POLICIES[policy.value], closed=int(stats[0]), open_ones=int(stats[1]))
+
+    def open_map(self):
+        """The open map as a uint8 array of shape dims (direct_cluster_get_open_map): the map before unobserved space was closed;
+        refused unless the last writer of the map was a successful "occupied" scan"""
+        g = np.zeros(self.dims, np.uint8)
+        _check(_lib().direct_cluster_get_open_map(self.h, abi.MEM_HOST, g.ctypes.data))
+        return g
 
     def frontiers(self, min_size=1, min_d2=0, capacity=1024, mem="host", voxel_labels=False):
         """Goal voxels on the boundary between observed and unobserved space (direct_cluster_frontier): the 26-connected components

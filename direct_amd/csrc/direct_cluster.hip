@@ -1000,6 +1000,7 @@ __global__ void k_emit(Dev D, int batch, int32_t* vertex_idx, int32_t* cluster_x
 #include "cluster_corridor.h"
 #include "map_scan.h"
 #include "map_evidence.h"
+#include "map_close.h"
 #include "frontier.h"
 #include "view_gain.h"
 
@@ -1076,6 +1077,10 @@ struct direct_cluster_handle_s {
   hipEvent_t evid_ev[6] = {};             // scan_timing: before the touch, behind the touch, the hit, the fold, the inflation and the table
   float evid_ms[5] = {0, 0, 0, 0, 0};
   bool evid_timed = false;
+  int32_t unknown_policy = DIRECT_UNKNOWN_FREE;  // what the NEXT scan does with unobserved voxels (direct_cluster_set_unknown_policy)
+  uint8_t* open_map = nullptr;             // the open map (the map's size and layout), allocated by the first scan under DIRECT_UNKNOWN_OCCUPIED
+  unsigned long long* close_cnt = nullptr; // [kCloseCounters] the close pass's own counters
+  int64_t close_stats[2] = {0, 0};         // closed, open_ones of the last successful scan under the policy
 };
 
 namespace {
@@ -1678,8 +1683,14 @@ direct_status_t scan_refusal(direct_cluster_handle_t h, const direct_map_scan_t*
   return DIRECT_OK;
 }
 
+// ... the bytes DIRECT_SCAN_ADOPT adopts: under DIRECT_UNKNOWN_OCCUPIED the open map where the handle holds one (the closed map
+// would turn unknown space into returns), the map otherwise; asked before the state's scan events ...
+const uint8_t* scan_adopts(direct_cluster_handle_t h) {
+  return h->unknown_policy == DIRECT_UNKNOWN_OCCUPIED && h->rs.has_open_map() ? h->open_map : h->map;
+}
+
 // ... what both allocate behind their refusals (the scan grid and its counters, the known grid of a tracked scan, the dilation
-// workspace of at least `ws_cells` grids, the cloud on the device) ...
+// workspace of at least `ws_cells` grids, the open map and its counters under DIRECT_UNKNOWN_OCCUPIED, the cloud on the device) ...
 direct_status_t scan_prepare(direct_cluster_handle_t h, const direct_map_scan_t* p, int64_t n_points, int32_t mem, const float* xyz,
                              size_t ws_cells, ScanDev* S) {
   const size_t cells = (size_t)h->D.G;
@@ -1687,6 +1698,8 @@ direct_status_t scan_prepare(direct_cluster_handle_t h, const direct_map_scan_t*
     CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->scan_raw, cells), hs::want(&h->scan_cnt, kScanCounters * sizeof(unsigned long long))}));
   const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
   if (track && !h->known) CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->known, cells)}));
+  if (h->unknown_policy == DIRECT_UNKNOWN_OCCUPIED && !h->open_map)
+    CHIP_TRY(hs::alloc_all(h->allocs, {hs::want(&h->open_map, cells), hs::want(&h->close_cnt, kCloseCounters * sizeof(unsigned long long))}));
   S->n = n_points; S->stride = p->stride; S->raw = h->scan_raw; S->cnt = h->scan_cnt; S->known = track ? h->known : nullptr;
   if (p->inflate[1] > 0 || p->inflate[2] > 0) ws_cells = std::max<size_t>(ws_cells, 2);
   if (ws_cells > 0) CHIP_TRY(hs::grow(h->scan_ws, h->stream, ws_cells * cells));
@@ -1703,6 +1716,9 @@ direct_status_t scan_finish(direct_cluster_handle_t h, const direct_map_scan_t* 
   const size_t cells = (size_t)h->D.G;
   const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
   auto tick = [&](int k) { return ev ? hipEventRecord(ev[k], h->stream) : hipSuccess; };
+  // DIRECT_UNKNOWN_OCCUPIED: the x pass goes into the open map in its non-counting form, and k_scan_close derives the map and counts
+  const bool close = h->unknown_policy == DIRECT_UNKNOWN_OCCUPIED;
+  if (e == hipSuccess && close) e = hipMemsetAsync(h->close_cnt, 0, kCloseCounters * sizeof(unsigned long long), h->stream);
   if (e == hipSuccess) {  // z, then y, through the workspace where they inflate at all; x last, into the map
     DilateDev P = {};
     P.size[0] = h->D.max_x; P.size[1] = h->D.max_y; P.size[2] = h->D.max_z;
@@ -1711,10 +1727,16 @@ direct_status_t scan_finish(direct_cluster_handle_t h, const direct_map_scan_t* 
     for (int axis = 2; axis >= 0; axis--) {
       if (axis > 0 && p->inflate[axis] == 0) continue;
       P.axis = axis; P.r = p->inflate[axis];
-      P.dst = axis == 0 ? h->map : (uint8_t*)h->scan_ws.p + (axis == 2 ? 0 : cells);
-      P.raw = axis == 0 ? h->scan_raw : nullptr;
+      P.dst = axis == 0 ? (close ? h->open_map : h->map) : (uint8_t*)h->scan_ws.p + (axis == 2 ? 0 : cells);
+      P.raw = axis == 0 && !close ? h->scan_raw : nullptr;
       hipLaunchKernelGGL(k_scan_dilate, dim3(blocks), dim3(256), 0, h->stream, P);
       P.src = P.dst;
+    }
+    if (close) {
+      CloseDev Q = {};
+      Q.G = (long long)cells; Q.open = h->open_map; Q.known = h->known; Q.raw = h->scan_raw; Q.map = h->map; Q.cnt = h->scan_cnt; Q.more = h->close_cnt;
+      const int close_blocks = (int)std::min<long long>((mcl::groups(Q.G) + 255) / 256, kScanMaxBlocks);
+      hipLaunchKernelGGL(k_scan_close, dim3(close_blocks), dim3(256), 0, h->stream, Q);
     }
     e = hipGetLastError();
   }
@@ -1722,6 +1744,8 @@ direct_status_t scan_finish(direct_cluster_handle_t h, const direct_map_scan_t* 
   unsigned long long cnt[kScanCounters] = {};
   if (e == hipSuccess) e = hipMemcpyAsync(cnt, h->scan_cnt, sizeof(cnt), hipMemcpyDeviceToHost, h->stream);
   if (e == hipSuccess && n_more > 0) e = hipMemcpyAsync(more, more_dev, n_more * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream);
+  unsigned long long closed[kCloseCounters] = {};
+  if (e == hipSuccess && close) e = hipMemcpyAsync(closed, h->close_cnt, sizeof(closed), hipMemcpyDeviceToHost, h->stream);
   e = hs::drain(h->stream, e);
   const bool changed = !had_map || cnt[kScanSet] + cnt[kScanCleared] > 0;
   if (e == hipSuccess && changed) e = rebuild_sat(h);  // nothing changed: the table, the field, the floor tables and the labels stay
@@ -1737,6 +1761,10 @@ direct_status_t scan_finish(direct_cluster_handle_t h, const direct_map_scan_t* 
   }
   h->rs.scan_ended(changed ? rs::ScanEnd::changed : rs::ScanEnd::unchanged);
   if (track) h->rs.known_ended(true);
+  if (close) {
+    h->rs.open_map_ready();
+    h->close_stats[0] = (int64_t)closed[kCloseClosed]; h->close_stats[1] = (int64_t)closed[kCloseOpenOnes];
+  }
   if (stats) {
     stats[0] = n_points; stats[1] = (int64_t)cnt[kScanSkipped]; stats[2] = (int64_t)cnt[kScanTruncated]; stats[3] = (int64_t)cnt[kScanOutside];
     stats[4] = (int64_t)cnt[kScanRawOnes]; stats[5] = (int64_t)cnt[kScanMapOnes]; stats[6] = (int64_t)cnt[kScanSet]; stats[7] = (int64_t)cnt[kScanCleared];
@@ -1750,6 +1778,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   if (!h || !p) return cfail(DIRECT_ERR_INVALID, "null argument");
   ScanDev S = {};
   if (const direct_status_t rc = scan_refusal(h, p, n_points, mem, xyz, &S)) return rc;
+  if (const char* why = mcl::scan_refusal(h->unknown_policy, p->flags)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const size_t cells = (size_t)h->D.G;
   const bool track = (p->flags & DIRECT_SCAN_TRACK_KNOWN) != 0;
@@ -1762,7 +1791,7 @@ direct_status_t direct_cluster_map_integrate_scan(direct_cluster_handle_t h, con
   hipError_t e = hipMemsetAsync(h->scan_cnt, 0, kScanCounters * sizeof(unsigned long long), h->stream);
   if (e == hipSuccess && !had_map) e = hipMemsetAsync(h->map, 0, cells, h->stream);  // the bytes "before" of a handle without a map
   if (e == hipSuccess) {
-    if (p->mode == DIRECT_SCAN_ADOPT) e = hipMemcpyAsync(h->scan_raw, h->map, cells, hipMemcpyDeviceToDevice, h->stream);
+    if (p->mode == DIRECT_SCAN_ADOPT) e = hipMemcpyAsync(h->scan_raw, scan_adopts(h), cells, hipMemcpyDeviceToDevice, h->stream);
     else if (p->mode == DIRECT_SCAN_RESET || !h->rs.has_scan_grid()) e = hipMemsetAsync(h->scan_raw, 0, cells, h->stream);
   }
   if (e == hipSuccess && track && (p->mode == DIRECT_SCAN_RESET || !h->rs.has_known())) e = hipMemsetAsync(h->known, 0, cells, h->stream);
@@ -1796,6 +1825,7 @@ direct_status_t direct_cluster_map_integrate_scan_evidence(direct_cluster_handle
   EvidDev E = {};
   E.P.hit = p->hit; E.P.miss = p->miss; E.P.ev_min = p->ev_min; E.P.ev_max = p->ev_max; E.P.occ = p->occ;
   if (const char* why = me::refusal(E.P, p->reserved)) return cfail(DIRECT_ERR_INVALID, why);
+  if (const char* why = mcl::scan_refusal(h->unknown_policy, sp->flags)) return cfail(DIRECT_ERR_INVALID, why);
   CHIP_TRY(hipSetDevice(h->cfg.device));
   const size_t cells = (size_t)h->D.G;
   const bool track = (sp->flags & DIRECT_SCAN_TRACK_KNOWN) != 0, adopt = sp->mode == DIRECT_SCAN_ADOPT;
@@ -1804,7 +1834,7 @@ direct_status_t direct_cluster_map_integrate_scan_evidence(direct_cluster_handle
     for (hipEvent_t& e : h->evid_ev) CHIP_TRY(hipEventCreate(&e));
   if (const direct_status_t rc = scan_prepare(h, sp, n_points, mem, xyz, 1, &S)) return rc;  // the touch grid: the workspace's first grid
   uint8_t* touch = (uint8_t*)h->scan_ws.p;
-  E.G = (long long)cells; E.touch = touch; E.ev = h->evid; E.map = adopt ? h->map : nullptr; E.raw = h->scan_raw; E.known = S.known; E.cnt = h->evid_cnt;
+  E.G = (long long)cells; E.touch = touch; E.ev = h->evid; E.map = adopt ? scan_adopts(h) : nullptr; E.raw = h->scan_raw; E.known = S.known; E.cnt = h->evid_cnt;
   const bool had_map = h->rs.has_map();
   auto tick = [&](int k) { return h->scan_timing ? hipEventRecord(h->evid_ev[k], h->stream) : hipSuccess; };
   CHIP_TRY(hs::start(h->ev, h->stream));
@@ -1898,6 +1928,28 @@ direct_status_t direct_cluster_get_scan_grid(direct_cluster_handle_t h, int32_t 
   if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
   if (!h->rs.has_scan_grid()) return cfail(DIRECT_ERR_INVALID, "the handle has no scan grid");
   return fetch_resident(h, mem, (size_t)h->D.G, raw, h->scan_raw);
+}
+
+direct_status_t direct_cluster_set_unknown_policy(direct_cluster_handle_t h, int32_t policy) {
+  if (!h) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mcl::policy_known(policy)) return cfail(DIRECT_ERR_INVALID, "policy is neither DIRECT_UNKNOWN_FREE nor DIRECT_UNKNOWN_OCCUPIED");
+  h->unknown_policy = policy;  // no grid is touched and no map event raised: the next scan derives the map under it
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_unknown_policy(direct_cluster_handle_t h, int32_t* policy, int64_t* stats2) {
+  if (!h || !policy) return cfail(DIRECT_ERR_INVALID, "null argument");
+  *policy = h->unknown_policy;
+  if (stats2)
+    for (int k = 0; k < 2; k++) stats2[k] = h->rs.has_open_map() ? h->close_stats[k] : 0;
+  return DIRECT_OK;
+}
+
+direct_status_t direct_cluster_get_open_map(direct_cluster_handle_t h, int32_t mem, uint8_t* out) {
+  if (!h || !out) return cfail(DIRECT_ERR_INVALID, "null argument");
+  if (!mem_kind(mem)) return cfail(DIRECT_ERR_INVALID, kMemRefusal);
+  if (!h->rs.has_open_map()) return cfail(DIRECT_ERR_INVALID, "the handle has no open map");
+  return fetch_resident(h, mem, (size_t)h->D.G, out, h->open_map);
 }
 
 direct_status_t direct_cluster_scan_phase_ms(direct_cluster_handle_t h, float* ms4) {
@@ -2653,7 +2705,7 @@ direct_status_t direct_cluster_view_gain_batch(direct_cluster_handle_t h, const 
   V.S.size[0] = h->D.max_x; V.S.size[1] = h->D.max_y; V.S.size[2] = h->D.max_z;
   V.S.R = vg::box_half(in->range_vox);
   V.S.R2 = in->range_vox * in->range_vox;
-  V.map = h->map; V.known = h->known;
+  V.map = h->rs.has_open_map() ? h->open_map : h->map; V.known = h->known;  // the rays stop at what was SEEN occupied
   V.n_dirs = in->n_dirs; V.n_sets = in->n_sets; V.words = vg::box_words(V.S.R);
   hs::Stage si(in->mem_in == DIRECT_MEM_HOST), so(in->mem == DIRECT_MEM_HOST);
   hs::stage_in(si, &V.voxel, io->voxel, n * 3 * sizeof(int32_t));

@@ -6,7 +6,7 @@
 //
 // Two properties the C boundary depends on:
 //   - All-zero bytes mean "nothing resident": every question answers from a zeroed object (no map, no valid field, no valid
-//     labels, no scan grid, no known grid, no evidence grid, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer
+//     labels, no scan grid, no known grid, no evidence grid, no open map, 0 clusters), and no question writes.  The ABI tests hand the library a zeroed buffer
 //     as a handle and assert that a refused call wrote not one byte of it.
 //   - No pointers, trivially copyable, a few dozen bytes.
 //
@@ -37,6 +37,7 @@ struct State {
   // whatever becomes of the call
   void map_edit_began() {
     field_valid_ = 0;
+    have_open_ = 0;  // the caller's bytes, or a scan's new map: an open map no longer stands beside them (see below)
     map_gen_++;
   }
   void map_lost() { have_map_ = 0; }   // a device error behind a write to the map: nothing describes its bytes
@@ -44,7 +45,8 @@ struct State {
   bool has_map() const { return have_map_ != 0; }
 
   // ---- the scan grid -----------------------------------------------------------------------------------------------------
-  void scan_began() { have_scan_ = 0; }  // map_integrate_scan touches the grids: not present until the call has ended well
+  // map_integrate_scan touches the grids: not present until the call has ended well - and neither is an open map
+  void scan_began() { have_scan_ = have_open_ = 0; }
   // unchanged: set + cleared == 0 on a handle that had a map - the table, the field, the floor tables and the labels stay
   void scan_ended(ScanEnd how) {
     if (how != ScanEnd::unchanged) map_edit_began();
@@ -67,6 +69,13 @@ struct State {
   // a PLAIN scan past its refusals (it writes the scan grid behind the evidence's back), a failed set_evidence
   void evidence_dropped() { have_evid_ = 0; }
   bool has_evidence() const { return have_evid_ != 0; }
+
+  // ---- the open map (the unknown policy DIRECT_UNKNOWN_OCCUPIED: the map as a scan derives it BEFORE unobserved space is closed;
+  // view_gain_batch and DIRECT_SCAN_ADOPT read it where it is held).  It stands beside the map of the scan that wrote both: any
+  // scan past its refusals loses it, and so do set_map and map_from_cloud past their null check (map_edit_began); a successful
+  // scan under the policy makes it ready again, a scan under DIRECT_UNKNOWN_FREE or a device error leaves it lost.
+  void open_map_ready() { have_open_ = 1; }  // behind scan_ended of a successful scan under the policy
+  bool has_open_map() const { return have_open_ != 0; }
 
   // ---- the distance field ------------------------------------------------------------------------------------------------
   void field_call_began() { field_gen_++; }    // every distance_field past its null check: labels built with a floor are stale
@@ -122,6 +131,7 @@ struct State {
   int32_t clusters_;
   int32_t have_known_;
   int32_t have_evid_;
+  int32_t have_open_;
 };
 static_assert(std::is_trivially_copyable<State>::value && std::is_standard_layout<State>::value, "plain data: zero bytes are a State");
 static_assert(sizeof(State) <= 256, "a handle is far smaller than the 64 KiB the ABI tests hand over");

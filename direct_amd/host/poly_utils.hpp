@@ -222,6 +222,32 @@ class polyhedronGenerator {
   void setKnown(const uint8_t* known) {
     if (direct_cluster_set_known(h_, DIRECT_MEM_HOST, known) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
   }
+  // What the scans make of voxels nobody has observed (direct_cluster_set_unknown_policy): DIRECT_UNKNOWN_FREE (the default: their
+  // map byte is 0) or DIRECT_UNKNOWN_OCCUPIED - every integrateScan / integrateScanEvidence, which must then be tracked, keeps
+  // two grids: the open map (what it derives under FREE) and the map, the open map with every unobserved voxel closed.  The
+  // planning calls read the map, viewGain the open map, frontiers gives the same goals on both.  Takes effect at the next scan.
+  void setUnknownPolicy(int policy) {
+    if (direct_cluster_set_unknown_policy(h_, policy) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+  }
+  struct UnknownPolicy {
+    int policy = DIRECT_UNKNOWN_FREE;
+    long long closed = 0, open_ones = 0;   // of the last successful scan under OCCUPIED: map 1 and open 0; the open map's ones
+  };
+  UnknownPolicy unknownPolicy() {
+    int32_t p = 0;
+    int64_t s[2] = {0, 0};
+    if (direct_cluster_get_unknown_policy(h_, &p, s) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    UnknownPolicy r;
+    r.policy = p; r.closed = s[0]; r.open_ones = s[1];
+    return r;
+  }
+  // the open map as the generator holds it, [x][y][z] (direct_cluster_get_open_map); throws unless the last writer of the map was
+  // a successful scan under DIRECT_UNKNOWN_OCCUPIED
+  std::vector<uint8_t> openMap() {
+    std::vector<uint8_t> m((size_t)mx_ * my_ * mz_);
+    if (direct_cluster_get_open_map(h_, DIRECT_MEM_HOST, m.data()) != DIRECT_OK) throw std::runtime_error(direct_cluster_last_error());
+    return m;
+  }
   // the map as the generator holds it, [x][y][z] (direct_cluster_get_map)
   std::vector<uint8_t> getMap() {
     std::vector<uint8_t> m((size_t)mx_ * my_ * mz_);

@@ -1047,6 +1047,47 @@ typedef struct {
 direct_status_t direct_cluster_view_gain_batch(direct_cluster_handle_t h, const direct_view_gain_in_t* in,
                                                const direct_view_gain_io_t* io);
 
+/* ---- unknown space as occupied: a closed planning map kept by the scans -----------------------------------------------
+ * Every planning call reads the map, and the map byte of a voxel nobody has observed is 0: paths, corridors, plan_check, the
+ * distance field and the free components take unobserved space for free.  The UNKNOWN POLICY of a handle says what the scans make
+ * of it.  DIRECT_UNKNOWN_FREE (the default, and what an all-zero handle means) is the behaviour described so far, kernel for
+ * kernel.  Under DIRECT_UNKNOWN_OCCUPIED every scan - direct_cluster_map_integrate_scan and ..._scan_evidence alike - derives TWO
+ * grids, all integer and exact; `raw` is the scan grid behind this scan's carve/mark or fold, `known` the known grid behind it:
+ *   open[v] = dilate(raw, inflate)[v]      the OPEN MAP: what the scan produces under DIRECT_UNKNOWN_FREE, byte for byte
+ *   map[v]  = open[v] | (known[v] == 0)    the MAP: unobserved voxels are closed.  Unknown space is NOT inflated.
+ * A known voxel is occupied in the map exactly when it is occupied in the open map, so the known, enterable voxels are the same
+ * under both policies, direct_cluster_frontier with min_d2 == 0 returns the same outputs, and every frontier representative stays a
+ * legal path goal.  Every planning call reads the map and is safe with no change of its own; direct_cluster_view_gain_batch reads
+ * the open map where the handle holds one (its rays must pass unknown voxels to count them) and the map otherwise.
+ * stats of a scan under the policy: [4] the ones of raw as before; [5] the ones of the MAP, [6] / [7] the voxels of the MAP set /
+ * cleared against the bytes the map held before.  The summed-area table is rebuilt, and the field, the floor tables and the labels
+ * go stale, only if the handle had no map or set + cleared > 0: a repeated scan that teaches nothing costs its kernels alone.
+ * The result depends neither on the order of the points nor on the launch shape.
+ * Under the policy a scan WITHOUT DIRECT_SCAN_TRACK_KNOWN is refused with DIRECT_ERR_INVALID, behind every other refusal of the
+ * call and before any write (an untracked scan drops the known grid; nothing would say what is known).  DIRECT_SCAN_ADOPT adopts
+ * the OPEN MAP where the handle holds one and the map otherwise - the plain scan's copy and the evidence fold's map operand:
+ * adopting the closed map would turn unknown space into returns.
+ * The open map is one more byte per voxel, allocated by the first scan under the policy.  The handle HOLDS an open map from a
+ * successful scan under the policy until the next scan past its refusals (a successful one under the policy leaves a new one; one
+ * under DIRECT_UNKNOWN_FREE, or a device error, leaves none) or the next direct_cluster_set_map / direct_cluster_map_from_cloud
+ * past its null check: those two write the caller's bytes verbatim under either policy.  direct_cluster_set_known changes only the
+ * known grid; the map follows at the next scan (a CONTINUE tracked scan of no points derives it at once).  It is the way to seed a
+ * known bubble around a vehicle whose sensor does not see its own surroundings.
+ * direct_cluster_set_unknown_policy: DIRECT_ERR_INVALID for a NULL handle or any other value, nothing written.  It touches no grid
+ * and raises no map event: the policy takes effect at the next scan.
+ * direct_cluster_get_unknown_policy: *policy, and in stats2 (host, or NULL) [0] closed = voxels with map == 1 and open == 0 and
+ * [1] open_ones = the ones of the open map, both of the last successful scan under the policy, zeros when the handle holds no
+ * open map.
+ * direct_cluster_get_open_map: out[max_x*max_y*max_z] in memory kind `mem`, as direct_cluster_get_map; DIRECT_ERR_INVALID, "the
+ * handle has no open map", unless the last writer of the map was a successful scan under DIRECT_UNKNOWN_OCCUPIED.
+ * Out of scope: inflating unknown space or a margin from it in metres (direct_cluster_plan_clearance_batch on the closed map
+ * reports the distance to the nearest unknown-or-occupied voxel); the outside of the map is not unknown space. */
+#define DIRECT_UNKNOWN_FREE     0
+#define DIRECT_UNKNOWN_OCCUPIED 1
+direct_status_t direct_cluster_set_unknown_policy(direct_cluster_handle_t h, int32_t policy);
+direct_status_t direct_cluster_get_unknown_policy(direct_cluster_handle_t h, int32_t* policy, int64_t* stats2 /* host [2] or NULL */);
+direct_status_t direct_cluster_get_open_map(direct_cluster_handle_t h, int32_t mem, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif
